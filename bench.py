@@ -1,7 +1,17 @@
 """Benchmark: MicroRank RCA windows on MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp64|fp32] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp64|fp32] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the line: metric / value / ms_per_step
+and the figures that fall out of the timed steps themselves (roofline of their own launches,
+window_roofline, step_ms).  Everything below that takes runs of its own -- the PMC traffic passes,
+the copy peak, the run-merged / isolated / single-window / kind-compressed legs, the c4_sharded leg
+and the CPU baseline -- is measured with --full only (where --no-traffic, --no-side, --no-c4-leg and
+--no-cpu drop single parts again).  --dump-outputs DIR writes what the last timed step returned to
+its caller as DIR/<name>.npy (float64): per window of the step top_codes / top_scores (rows padded
+to 11 with -1 / 0) / top_count / n_abnormal / n_normal / edges; c4 / c5: weights / coverage.  The
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 Workload (BASELINE.json configs[1], "C2"): RCA windows of 1k operations / 200k traces each
 (~13.7 spans per trace, ~2.74M spans per window; Train-Ticket-like synthetic call tree with one
@@ -73,22 +83,115 @@ def _c2_abnormal(job):
     return st
 
 
-def c2_windows(n: int, n_ops: int, n_traces: int, rank: int):
-    """n DISTINCT C2 windows of one system (BASELINE configs[1]: 1k ops / 200k traces each): one
-    topology and normal SLO period, each window's traffic from its own seed (a 5-minute window of a
-    different time).  Generated in a process pool before this process touches the GPU.  Returns
-    (normal SpanTable, [abnormal SpanTable] * n)."""
-    from concurrent.futures import ProcessPoolExecutor
+# Span columns in the order a slot of c2_window_stream's slab holds them (8-byte columns first, so
+# every column starts aligned whatever the span count)
+_SLOT_COLS = (("span", np.int64), ("parent", np.int64), ("duration", np.int64), ("tstart", np.int64),
+              ("tend", np.int64), ("trace", np.int32), ("podop", np.int32), ("svcop", np.int32))
+_SLAB = None   # (shared anonymous mmap, bytes per slot, turn per slot, its condition): set before the pool forks
+
+
+def _c2_table(job):
+    """Pool worker of c2_window_stream: table `i` of the stream (0: the normal period, i > 0:
+    abnormal window i - 1) with its columns written into slot i % slots of the slab the worker
+    inherited -- 142 MB per C2 table that never cross a pipe.  The slot is written when it is
+    table i's turn (turn[slot] == i: the consumer is done with table i - slots), so tables that
+    share a slot use it in stream order however long each takes to generate.  Returns (spans,
+    pod-op names, service-op names); a table larger than a slot comes back whole."""
+    from microrank_amd import synth
+
+    i, topo, n_traces, seed = job
+    if i == 0:
+        st = synth.gen_spans(topo, n_traces, seed, branch=1.9, p_max=0.8, names=False)
+        st.trace_names = None
+    else:
+        st = _c2_abnormal((topo, n_traces, seed))
+    buf, slot_bytes, turn, moved = _SLAB
+    S = st.n_spans
+    if S * sum(np.dtype(t).itemsize for _, t in _SLOT_COLS) > slot_bytes:
+        st.meta = {}
+        return st
+    slot = i % len(turn)
+    with moved:
+        moved.wait_for(lambda: turn[slot] == i)
+    off = slot * slot_bytes
+    for name, t in _SLOT_COLS:
+        a = np.frombuffer(buf, t, S, off)
+        a[:] = getattr(st, name)
+        off += a.nbytes
+    return S, st.podop_names, st.svcop_names
+
+
+def c2_window_stream(n: int, n_ops: int, n_traces: int, rank: int, slots: int | None = None):
+    """The tables of n DISTINCT C2 windows of one system (BASELINE configs[1]: 1k ops / 200k traces
+    each): one topology and normal SLO period, each window's traffic from its own seed (a 5-minute
+    window of a different time).  Returns an iterator over n + 1 SpanTables: the normal period, then
+    the n abnormal windows in order.  The process pool that generates them is forked HERE, before
+    the caller touches the GPU; the tables are then handed over as they are ready, so that the caller
+    can upload one while the next ones are generated.  A table's columns are views of a shared
+    slab (`slots` tables of room, default two per worker, at least two) and hold its values only
+    until the next table is taken: copy (own_table) what must live longer.  That is also when the
+    slot goes to its next writer, so whoever reads a table asynchronously must have finished by
+    then (mr_spans_upload has: it returns after synchronising the stream its copies ran on)."""
+    global _SLAB
+    import mmap
+    import multiprocessing as mp
+
+    from microrank_amd import synth
+    from microrank_amd.spans import SpanTable
 
     seed = 1234 + 7919 * rank
-    topo, normal, first = make_window(seed, n_ops, n_traces)
-    jobs = [(topo, n_traces, seed + 2 + 104729 * i) for i in range(1, n)]
+    topo = synth.make_topology(n_ops, seed)
+    jobs = [(0, topo, n_traces, seed + 1)] + [(i + 1, topo, n_traces, seed + 2 + 104729 * i) for i in range(n)]
     threads, _ = host_cores()
-    if not jobs:
-        return normal, [first]
-    with ProcessPoolExecutor(max_workers=max(1, min(16, threads, len(jobs)))) as ex:
-        rest = list(ex.map(_c2_abnormal, jobs))
-    return normal, [first] + rest
+    workers = max(1, min(16, threads, len(jobs)))
+    # at least two slots: table i's slot is passed on when table i + 1 is taken, and the writer
+    # waiting for it (table i + slots) must not be the one that table i + 1 is waiting for
+    slots = max(2, 2 * workers if slots is None else slots)
+    row = sum(np.dtype(t).itemsize for _, t in _SLOT_COLS)
+    slot_bytes = -(-(row * 24 * n_traces) // mmap.PAGESIZE) * mmap.PAGESIZE   # ~13.7 spans per trace: room for 24
+    fork = mp.get_context("fork")
+    buf = mmap.mmap(-1, slots * slot_bytes)   # anonymous + shared: pages exist once written
+    turn = fork.RawArray("q", range(slots))   # per slot: the table whose turn it is to write it
+    moved = fork.Condition()
+    _SLAB = (buf, slot_bytes, turn, moved)
+    pool = fork.Pool(workers)   # every worker forks now
+    _SLAB = None
+
+    def tables():
+        try:
+            for i, res in enumerate(pool.imap(_c2_table, jobs)):
+                if i:   # the consumer is done with table i - 1: its slot to table i - 1 + slots
+                    with moved:
+                        turn[(i - 1) % slots] = i - 1 + slots
+                        moved.notify_all()
+                if isinstance(res, SpanTable):
+                    yield res
+                    continue
+                S, podop_names, svcop_names = res
+                off, cols = (i % slots) * slot_bytes, {}
+                for name, t in _SLOT_COLS:
+                    cols[name] = np.frombuffer(buf, t, S, off)
+                    off += cols[name].nbytes
+                yield SpanTable(podop_names=podop_names, svcop_names=svcop_names, **cols)
+        finally:
+            pool.terminate()
+            pool.join()
+
+    return tables()
+
+
+def own_table(st):
+    """A copy of a SpanTable of c2_window_stream with columns of its own (copied out of the slab)."""
+    import dataclasses
+
+    return dataclasses.replace(st, **{name: np.array(getattr(st, name)) for name, _ in _SLOT_COLS})
+
+
+def c2_windows(n: int, n_ops: int, n_traces: int, rank: int):
+    """c2_window_stream collected: (normal SpanTable, [abnormal SpanTable] * n), every table with
+    columns of its own."""
+    tabs = [own_table(st) for st in c2_window_stream(n, n_ops, n_traces, rank)]
+    return tabs[0], tabs[1:]
 
 
 def slo_from_gpu(ctx, normal):
@@ -465,7 +568,10 @@ def run_c4(args, world, rank, dist):
                        "5% broken traces, 1% duplicated root spanIDs across ranks), int-coded, resident in HBM")
         out["config"]["n_spans_rank0"] = int(n_spans_local)
         out["build_ms"] = round(build_s[0] / args.steps * 1e3, 3)   # rank 0's K1 share of a step
-    add_copy_frac(out, ctx)
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, {"weights": w, "coverage": cov})
+    if args.full:
+        add_copy_frac(out, ctx)
     if not args.no_cpu and world == 1 and dev is None:
         try:
             out["cpu_baseline"] = c4_cpu_baseline(hg)
@@ -1056,12 +1162,36 @@ def emit(obj):
     out.flush()
 
 
+def dump_arrays(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (integers up to 2^53 are exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_windows(dirname, results, k=11):
+    """--dump-outputs of the window configs: what the last timed step's calls returned per window
+    (codes, scores, n_abnormal, n_normal, edges), in the step's window order.  A window's top list
+    has top_count entries; the rows of top_codes / top_scores are padded to k with -1 / 0."""
+    n = len(results)
+    codes, scores = np.full((n, k), -1.0), np.zeros((n, k))
+    for i, r in enumerate(results):
+        codes[i, :len(r[0])] = r[0]
+        scores[i, :len(r[1])] = r[1]
+    dump_arrays(dirname, {"top_codes": codes, "top_scores": scores, "top_count": [len(r[0]) for r in results],
+                          "n_abnormal": [r[2] for r in results], "n_normal": [r[3] for r in results],
+                          "edges": [r[4] for r in results]})
+
+
 def main():
     claim_stdout()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 20; c3 and sweep 3, ingest and dropin 5)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="warm-up steps (default 3; c3, sweep, ingest and dropin 1).  c4 / c5 run at least one, "
+                         "also with --warmup 0: the first call makes the once-per-graph exchange")
     ap.add_argument("--precision", choices=["fp64", "fp32"], default=None,
                     help="default fp64 (c2, c4), fp32 (c5: BASELINE configs[4])")
     ap.add_argument("--ops", type=int, default=1000)
@@ -1103,7 +1233,24 @@ def main():
                     help="write /proc/self/maps here after the warm-up (resolving native stack frames of a crash)")
     ap.add_argument("--c2-distinct", type=int, default=None,
                     help="c2: distinct seeded windows per step (default: every window of the step distinct)")
+    ap.add_argument("--full", action="store_true",
+                    help="c2/c3/c4/c5: beside the timed steps, every side measurement of the line -- PMC traffic "
+                         "(child runs), copy peak, run-merged / isolated / single-window / kind-compressed legs, the "
+                         "c4_sharded leg, the CPU baseline (each can be dropped again: --no-traffic, --no-side, "
+                         "--no-c4-leg, --no-cpu).  Without it: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="c2/c3/c4/c5: after the timed steps, write what the last timed step returned to its caller "
+                         "as DIR/<name>.npy (float64; rank 0)")
     args = ap.parse_args()
+    d_steps, d_warmup = {"c3": (3, 1), "sweep": (3, 1), "ingest": (5, 1), "dropin": (5, 1)}.get(args.config, (20, 3))
+    args.steps = d_steps if args.steps is None else args.steps
+    args.warmup = d_warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config in ("sweep", "stream", "ingest", "dropin"):
+        ap.error(f"--dump-outputs: not available for --config {args.config}")
+    if not args.full:   # a plain run measures its headline only
+        args.no_traffic = args.no_cpu = args.no_side = True
     if args.streams is None:
         # c3: a 4096-window batch in calls of 2048 (r04: 256 / 512 / 1024 / 2048 / 4096 windows per
         # call 26.0-26.6k / 28.4-28.6k / 29.2-30.1k / 30.1k / 29.2-30.3k windows/s, profiles/r04aa);
@@ -1119,10 +1266,6 @@ def main():
         args.c4_traces = 100_000_000 if args.config == "c5" else 10_000_000
     if args.config == "c3":   # BASELINE configs[2]: 500 ops / 20k traces per window
         args.ops, args.traces = 500, 20_000
-        if "--steps" not in sys.argv:
-            args.steps = 3
-        if "--warmup" not in sys.argv:
-            args.warmup = 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1138,10 +1281,6 @@ def main():
         dist.init_process_group("gloo")
     os.environ.setdefault("MICRORANK_DEVICE", str(local))
     if args.config in ("sweep", "stream", "ingest", "dropin"):   # single-GPU supplementary lines (f2 / f3 / drop-in)
-        if args.config in ("ingest", "dropin") and "--steps" not in sys.argv:
-            args.steps, args.warmup = 5, 1
-        if args.config == "sweep" and "--steps" not in sys.argv:
-            args.steps, args.warmup = 3, 1
         out = {"sweep": run_sweep, "stream": run_stream, "ingest": run_ingest, "dropin": run_dropin}[args.config](args)
         emit(out)
         return
@@ -1178,12 +1317,10 @@ def main():
             c4_hg = c4_leg_generate(world, rank)
         except Exception as e:   # (a side leg never sinks the line)
             c4_hg = e
-    if batch and args.config == "c2":   # distinct windows, generated before the GPU is touched
+    if batch and args.config == "c2":   # distinct windows: their generators fork before the GPU is touched
         nd = W if args.c2_distinct is None else max(1, min(W, args.c2_distinct))
         t_gen = time.perf_counter()
-        c2_tabs = c2_windows(nd, args.ops, args.traces, rank)
-        print(f"[bench] rank {rank}: {nd} distinct C2 windows generated in {time.perf_counter() - t_gen:.1f} s",
-              file=sys.stderr, flush=True)
+        c2_tabs = c2_window_stream(nd, args.ops, args.traces, rank)
     # batch (default): one context; a step is ONE mr_windows_batch call over W windows (their
     # detectors / builds / spectra on the library's auxiliary streams, their PageRanks sharing
     # each iteration's launches).  --streams-mode: W contexts driven by W host threads, one
@@ -1196,17 +1333,20 @@ def main():
     D = max(1, args.c3_distinct) if args.config == "c3" else 1
     wins = [[] for _ in range(1 if batch else W)]   # per context: [(dev, t0, t1, a3, ok, abnormal)]
     if c2_tabs is not None:
-        normal, tabs = c2_tabs
-        a3, ok = slo_from_gpu(ctxs[0], normal)   # one SLO period; every table has the topology's codes
-        for i, abnormal_i in enumerate(tabs):
+        # each table is uploaded as it arrives, while the pool generates the next ones
+        a3, ok = slo_from_gpu(ctxs[0], next(c2_tabs))   # one SLO period; every table has the topology's codes
+        for i, abnormal_i in enumerate(c2_tabs):
+            if i == 0:   # window 0 is kept on the host (it feeds the CPU baseline): a copy outside the slab
+                abnormal_i = own_table(abnormal_i)
             t0 = int(abnormal_i.tstart.min())
-            dev_i = DeviceSpans(ctxs[0], abnormal_i)
-            if i:   # host copy no longer needed (window 0's feeds the CPU baseline): ~140 MB a window
+            dev_i = DeviceSpans(ctxs[0], abnormal_i)   # (returns with the columns copied: the slot may move on)
+            if i:   # the others' host columns are slab views that the next tables overwrite: dropped
                 dev_i.table = None
-                tabs[i] = None
             wins[0].append((dev_i, t0, t0 + 5 * 60 * 10**9, a3, ok, abnormal_i if i == 0 else None))
-            del abnormal_i
-        abnormal, topo = tabs[0], None
+            del abnormal_i, dev_i
+        print(f"[bench] rank {rank}: {len(wins[0])} distinct C2 windows generated and uploaded in "
+              f"{time.perf_counter() - t_gen:.1f} s", file=sys.stderr, flush=True)
+        topo = normal = None
         D = 0
     for d in range(D):
         seed = 1234 + 7919 * rank + 104729 * d
@@ -1245,6 +1385,7 @@ def main():
             dist.barrier()
 
     step_times = []   # (batch mode) wall time of each step of the last run_all, ms
+    last_step = []    # what the last step of the last run_all returned per window (--dump-outputs)
 
     def run_all(n):
         """n steps; (edges, windows, the first window's last result).  c2: a step is W windows;
@@ -1258,6 +1399,7 @@ def main():
             step_times.clear()
             for _ in range(n):
                 ts_step = time.perf_counter()   # (each call returns its results: synchronous)
+                last_step.clear()
                 for c0 in range(0, per_step, W):   # c3: calls of <= W windows
                     idx = range(c0, min(per_step, c0 + W))
                     out = rank_windows(ctx, [pool[j % len(pool)][:5] for j in idx],
@@ -1268,6 +1410,7 @@ def main():
                         res.append(e_)
                         if j % len(pool) == 0:
                             first = (e_, codes, scores, na_, nn_)
+                    last_step.extend(out)
                 step_times.append((time.perf_counter() - ts_step) * 1e3)
             return sum(res), len(res), first
 
@@ -1285,6 +1428,9 @@ def main():
 
             with ThreadPoolExecutor(max_workers=W) as ex:
                 outs = list(ex.map(one, range(W)))
+        # the last step: each context's last share of windows, as rank_windows orders a result
+        last_step[:] = [(r[1], r[2], r[3], r[4], r[0]) for ci, o in enumerate(outs)
+                        for r in (o[len(o) - (per_ctx[ci] if per_ctx is not None else 1):] if n > 0 else [])]
         # the last result of context 0's first window (the one the CPU baseline re-ranks)
         last0 = outs[0][(len(outs[0]) - 1) // len(wins[0]) * len(wins[0])] if outs[0] else None
         return sum(r[0] for o in outs for r in o), sum(len(o) for o in outs), last0
@@ -1301,6 +1447,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t_start
     e, top, scores, na, nn = last
+    if args.dump_outputs and rank == 0:
+        dump_windows(args.dump_outputs, last_step)
     import ctypes as C
 
     launches, kms, kbytes = C.c_int64(), C.c_double(), C.c_double()
@@ -1391,7 +1539,8 @@ def main():
                                       "what": "B_iter with 2 B per (trace, op) pair: k_tr_a reads u16 op ids"}
     add_pmc_frac(out, traffic)
     if args.no_side:
-        add_copy_frac(out, ctx)
+        if args.full:
+            add_copy_frac(out, ctx)
         emit(out)
         if dist is not None:
             dist.barrier()

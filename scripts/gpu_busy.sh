@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: kernel trace of a bench run -> busy union / concurrency / kernel shares of its last SPAN ms
 #   scripts/gpu_busy.sh TAG SPAN_MS [bench args...]
+#   traces set-up, warm-up and the timed steps only; give --full among the bench args to trace the side legs too
 TAG=$1; SPAN=$2; shift 2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out

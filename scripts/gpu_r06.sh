@@ -15,11 +15,11 @@ if has s; then
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.txt 2>&1 || { tail -5 ${O}_smoke.txt; exit 1; }
 fi
 if has c2; then
-  timeout -k 10 900 python3 bench.py > ${O}_c2.json 2> ${O}_c2.err || { tail -5 ${O}_c2.err; exit 1; }
+  timeout -k 10 900 python3 bench.py --full > ${O}_c2.json 2> ${O}_c2.err || { tail -5 ${O}_c2.err; exit 1; }
   cut -c1-600 ${O}_c2.json
 fi
 if has c2ns; then
-  timeout -k 10 600 python3 bench.py --no-traffic --no-cpu --no-c4-leg > ${O}_c2ns.json 2> ${O}_c2ns.err || { tail -5 ${O}_c2ns.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --no-traffic --no-cpu --no-c4-leg > ${O}_c2ns.json 2> ${O}_c2ns.err || { tail -5 ${O}_c2ns.err; exit 1; }
   cut -c1-600 ${O}_c2ns.json
 fi
 if has prof; then
@@ -27,7 +27,7 @@ if has prof; then
 fi
 for c in c3 c4 c5; do
   if has $c; then
-    timeout -k 10 600 python3 bench.py --config $c > ${O}_$c.json 2> ${O}_$c.err || { tail -5 ${O}_$c.err; exit 1; }
+    timeout -k 10 600 python3 bench.py --config $c --full > ${O}_$c.json 2> ${O}_$c.err || { tail -5 ${O}_$c.err; exit 1; }
     cut -c1-500 ${O}_$c.json
   fi
 done

@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: kernel trace of a bench run -> a bucketed timeline of SPAN ms from the timed steps
 #   scripts/gpu_timeline.sh TAG SPAN_MS BUCKET_US [bench args...]
+#   traces set-up, warm-up and the timed steps only; give --full among the bench args to trace the side legs too
 TAG=$1; SPAN=$2; BK=$3; shift 3
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out

@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: rocprofv3 kernel stats of a bench command -> gpurun_out/pb_TAG/ + top kernels
 #   scripts/prof_bench.sh TAG [bench args...]
+#   traces set-up, warm-up and the timed steps only; give --full among the bench args to trace the side legs too
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out

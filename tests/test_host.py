@@ -168,3 +168,53 @@ def test_fingerprint_reads_subset():
     assert not fp.matches(df, GRAPH_READS) and not fp.matches(df)
     df.loc[df.index[7], "duration"] = -1
     assert not fp.matches(df, DETECT_READS)
+
+
+def test_bench_window_stream_hands_over_the_generators_tables():
+    """bench.py's c2_window_stream (tables generated in a forked pool, their columns handed over
+    through a shared slab whose slots are reused) yields exactly what the generator makes in this
+    process: the normal period, then every window from its own seed.  41 tables: more than the
+    slab's slots (at most 32), so slots are reused while earlier tables are still being read; then
+    with two slots and one slow worker, where the tables of a slot are ready out of order."""
+    import bench
+
+    n, n_ops, n_traces, rank = 40, 20, 500, 1
+    seed = 1234 + 7919 * rank
+    topo, normal, first = bench.make_window(seed, n_ops, n_traces)
+    want = [normal, first] + [bench._c2_abnormal((topo, n_traces, seed + 2 + 104729 * i)) for i in range(1, n)]
+    cols = ("trace", "podop", "svcop", "span", "parent", "duration", "tstart", "tend")
+    got = 0
+    for st, ref in zip(bench.c2_window_stream(n, n_ops, n_traces, rank), want):
+        for c in cols:
+            a, b = getattr(st, c), getattr(ref, c)
+            assert a.dtype == b.dtype and np.array_equal(a, b), (got, c)
+        assert list(st.podop_names) == list(ref.podop_names) and list(st.svcop_names) == list(ref.svcop_names)
+        assert st.trace_names is None and st.n_traces == ref.n_traces
+        got += 1
+    assert got == n + 1
+    # two slots, and table 1 slow to generate: tables 3, 5, ... of the same slot are ready long
+    # before it and must still wait for their turn (every slot is reused many times)
+    import time
+
+    slow_seed, make = seed + 2, bench._c2_abnormal
+
+    def delayed(job):
+        if job[2] == slow_seed:
+            time.sleep(0.3)
+        return make(job)
+
+    bench._c2_abnormal = delayed   # (the forked workers inherit it)
+    try:
+        stream = bench.c2_window_stream(12, n_ops, n_traces, rank, slots=2)
+    finally:
+        bench._c2_abnormal = make
+    got = 0
+    for st, ref in zip(stream, want):
+        assert all(np.array_equal(getattr(st, c), getattr(ref, c)) for c in cols), got
+        got += 1
+    assert got == 13
+    # collected: tables with columns of their own, alive after the stream has ended
+    nrm, tabs = bench.c2_windows(3, n_ops, n_traces, rank)
+    assert len(tabs) == 3
+    for st, ref in zip([nrm] + tabs, want):
+        assert all(np.array_equal(getattr(st, c), getattr(ref, c)) for c in cols)
