@@ -231,6 +231,28 @@ int mr_spectrum(mr_ctx* ctx, int32_t n, const uint8_t* has_a, const double* a_w,
 int mr_slo(mr_ctx* ctx, const mr_spans* s, double* mean /*[n_svcops]*/, double* std_ /*[n_svcops]*/,
            int64_t* count /*[n_svcops]*/);
 
+/* K4, percentile form: per service-op code, the q[j]-quantiles of the span durations, with
+ * numpy.quantile's semantics (bit for bit on int64 durations).  No reference counterpart: extends
+ * preprocess_data.get_operation_slo (preprocess_data.py:50-78) so that the detector's per-op
+ * expectation can be a p99 instead of mean + 3*std (a percentile SLO is handed on as [Q, 0.0]).
+ * Rows: all of the table when t0 == INT64_MIN and t1 == INT64_MAX, otherwise the rows with
+ * tstart >= t0 && tend <= t1 (mr_detect's inclusive window); a window on a table uploaded
+ * without trace-level times returns MR_ERR_STATE.
+ * method: numpy's method= names.  With n rows of an op sorted ascending as a[0..n) and
+ * vi = (double)(n-1) * q:  LOWER a[floor(vi)], HIGHER a[ceil(vi)], LINEAR numpy's _lerp between
+ * a[floor(vi)] and its successor with g = vi - floor(vi) (taken from the upper end for g >= 0.5).
+ * out[o * n_q + j] is in duration units, not scaled and not rounded; count[o] = rows of op o that
+ * took part; count 0 gives out = 0.0, as mr_slo does.
+ * MR_ERR_ARG: null pointers, n_q < 1, an unknown method, a q[j] that is NaN or outside [0, 1], s of
+ * another context, or a duration range too wide to sort: grouping and ordering are ONE sort of
+ * keys (op << DB) | (duration - min), DB = bits of (max - min) over the rows that take part, and
+ * bits(n_svcops) + DB must not exceed 64 (with 1k ops: a duration spread below 2^54).
+ * n_svcops == 0 returns MR_OK and writes nothing; an empty table or a window that selects no row
+ * returns MR_OK with every count 0. */
+enum { MR_Q_LINEAR = 0, MR_Q_LOWER = 1, MR_Q_HIGHER = 2 };
+int mr_slo_quantiles(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* q, int32_t n_q,
+                     int method, double* out /*[n_svcops * n_q] host*/, int64_t* count /*[n_svcops] host*/);
+
 /* ------------------------------------------------------------------ K5: detector
  * anormaly_detector.system_anomaly_detect (anormaly_detector.py:44-84) with
  * get_operation_duration_data (preprocess_data.py:97-122): window [t0, t1] on trace-level

@@ -19,6 +19,9 @@ MR_OK, MR_ERR_ARG, MR_ERR_HIP, MR_ERR_VALUE, MR_ERR_ZERODIV, MR_ERR_OOM, MR_ERR_
 MR_FP64, MR_FP32 = 0, 1
 MR_PR_EXACT_SUMS = 1
 MR_PR_KIND_COMPRESS = 2   # mr_pagerank: iterate over one representative per trace kind (§8(f) f4)
+MR_Q_LINEAR, MR_Q_LOWER, MR_Q_HIGHER = 0, 1, 2   # mr_slo_quantiles: numpy.quantile's method= names
+QUANTILE_METHODS = {"linear": MR_Q_LINEAR, "lower": MR_Q_LOWER, "higher": MR_Q_HIGHER}
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1   # mr_slo_quantiles: t0 / t1 of "the whole table"
 
 SPECTRUM_METHODS = ("dstar2", "ochiai", "jaccard", "sorensendice", "m1", "m2", "goodman", "tarantula",
                     "russellrao", "hamann", "dice", "simplematcing", "rogers")
@@ -93,6 +96,7 @@ SIGNATURES = {
     "mr_spectrum": (C.c_int, [P, C.c_int32, u8p, f64p, i64p, u8p, f64p, i64p, C.c_int64, C.c_int64,
                               C.c_int, C.c_int32, i32p, f64p, i32p, i32p]),
     "mr_slo": (C.c_int, [P, P, f64p, f64p, i64p]),
+    "mr_slo_quantiles": (C.c_int, [P, P, C.c_int64, C.c_int64, f64p, C.c_int32, C.c_int, f64p, i64p]),
     "mr_detect": (C.c_int, [P, P, C.c_int64, C.c_int64, f64p, u8p, u8p, i32p, i32p, i64p]),
     "mr_detect_sweep": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, f64p, u8p, u8p, i32p, i32p,
                                   i64p]),

@@ -22,12 +22,13 @@ from .preprocess_data import DETECT_READS, get_operation_slo, get_service_operat
 from .spans import to_ns
 
 
-def get_slo(span_df, start_time=None, end_time=None, *, ctx=None):
-    """SLO of every service operation of ``span_df`` (optionally restricted to the window)."""
+def get_slo(span_df, start_time=None, end_time=None, *, ctx=None, quantile=None, method="linear"):
+    """SLO of every service operation of ``span_df`` (optionally restricted to the window); with
+    ``quantile`` the percentile SLO [Q, 0.0] of ``get_operation_slo``."""
     df = get_span(span_df, start_time, end_time)
     df = df.copy() if df is not span_df else df
     operation_list = get_service_operation_list(df)
-    return get_operation_slo(operation_list, df, ctx=ctx)
+    return get_operation_slo(operation_list, df, ctx=ctx, quantile=quantile, method=method)
 
 
 def slo_arrays(table, slo):

@@ -5,7 +5,9 @@
   with the reference's key order and list contents.  Passing them straight to
   ``pagerank.trace_pagerank`` (what ``online_anomaly_detect_RCA`` does) keeps the graph in
   HBM: no dict is ever materialised.
-* ``get_operation_slo`` runs the SLO reduction on the GPU (K4, csrc/mr_slo.hip).
+* ``get_operation_slo`` runs the SLO reduction on the GPU (K4, csrc/mr_slo.hip);
+  ``get_operation_quantiles`` / ``get_operation_slo(..., quantile=q)`` the percentile form
+  (csrc/mr_quantile.hip; no reference counterpart).
 * ``get_span``, ``get_service_operation_list`` and ``get_operation_duration_data`` are
   DataFrame utilities with the reference's behaviour (including the added ``operation``
   column side effect).
@@ -26,7 +28,7 @@ import pandas as pd
 
 from . import _lib
 from ._lib import SpanCols, ptr
-from .spans import UI_SERVICE, IngestedTable, SpanTable, _as_ns, arrow_columns, op_display
+from .spans import UI_SERVICE, IngestedTable, SpanTable, _as_ns, arrow_columns, op_display, to_ns
 
 ROOT_INDEX = "root"   # preprocess_data.py:7
 
@@ -388,9 +390,60 @@ def get_service_operation_list(span_df: pd.DataFrame):
     return span_df["operation"].drop_duplicates().tolist()
 
 
-def get_operation_slo(service_operation_list, span_df: pd.DataFrame, *, ctx=None):
+def _quantile_args(q, method):
+    """(q as a contiguous float64 vector, MR_Q_* code); ValueError for a q outside [0, 1] (or NaN)
+    and for a method other than numpy's 'linear', 'lower', 'higher'."""
+    code = _lib.QUANTILE_METHODS.get(method) if isinstance(method, str) else None
+    if code is None:
+        raise ValueError(f"method must be one of {sorted(_lib.QUANTILE_METHODS)}, not {method!r}")
+    try:
+        qv = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    except (TypeError, ValueError):
+        raise ValueError(f"q must be a float or a sequence of floats in [0, 1], not {q!r}") from None
+    if qv.ndim != 1 or qv.size == 0 or not np.all((qv >= 0.0) & (qv <= 1.0)):
+        raise ValueError(f"q must be a float or a non-empty sequence of floats in [0, 1], not {q!r}")
+    return qv, code
+
+
+def get_operation_quantiles(service_operation_list, span_df: pd.DataFrame, q, *, method="linear", window=None,
+                            ctx=None):
+    """Per-operation duration quantiles on the GPU (K4, csrc/mr_quantile.hip; no reference
+    counterpart): {svc_op: [round(Q_j/1000, 4) for q_j in q]} with ``np.quantile``'s semantics
+    (``method`` 'linear', 'lower' or 'higher'), for the ops of the DataFrame that are in
+    ``service_operation_list`` and have a span, keys in sorted order like ``get_operation_slo``.
+    ``window=(start, end)`` restricts the rows to the detector's inclusive trace-level window."""
+    qv, code = _quantile_args(q, method)
+    span_df["operation"] = _svc_op_names(span_df)
+    ctx = ctx or _lib.default_context()
+    table, dev = span_table(span_df, ctx)
+    t0, t1 = _lib.INT64_MIN, _lib.INT64_MAX
+    if window is not None:
+        t0, t1 = to_ns(window[0]), to_ns(window[1])
+    n = table.n_svcops
+    out = np.zeros((n, qv.size), np.float64)
+    cnt = np.zeros(n, np.int64)
+    ctx.check(_lib.load().mr_slo_quantiles(ctx.h, dev.h, t0, t1, ptr(qv, C.c_double), qv.size, code,
+                                           ptr(out, C.c_double), ptr(cnt, C.c_int64)), "mr_slo_quantiles")
+    ms = np.round(out / 1000.0, 4)   # the SLO's ms scaling and rounding (preprocess_data.py:72-73)
+    keep = set(service_operation_list)
+    res = {}
+    for op, name in enumerate(table.svcop_names):   # codes are in sorted name order
+        if cnt[op] > 0 and name in keep:
+            res[name] = [np.float64(v) for v in ms[op]]
+    return res
+
+
+def get_operation_slo(service_operation_list, span_df: pd.DataFrame, *, ctx=None, quantile=None, method="linear"):
     """preprocess_data.py:50-78 on the GPU (K4): {svc_op: [round(mean/1000,4), round(std/1000,4)]}
-    for the ops of the DataFrame that are in ``service_operation_list``, keys in sorted order."""
+    for the ops of the DataFrame that are in ``service_operation_list``, keys in sorted order.
+    With ``quantile`` (a float in [0, 1]) the percentile SLO instead: {svc_op: [Q, 0.0]}, Q the
+    op's ``quantile`` of the durations (``get_operation_quantiles``), so that the detector's
+    mean + 3 * std is Q."""
+    if quantile is not None:
+        if np.ndim(quantile) != 0:
+            raise ValueError(f"quantile must be one float in [0, 1], not {quantile!r}")
+        qs = get_operation_quantiles(service_operation_list, span_df, quantile, method=method, ctx=ctx)
+        return {name: [v[0], np.float64(0.0)] for name, v in qs.items()}
     span_df["operation"] = _svc_op_names(span_df)
     ctx = ctx or _lib.default_context()
     table, dev = span_table(span_df, ctx)
