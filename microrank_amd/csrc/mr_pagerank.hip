@@ -45,9 +45,9 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-__global__ void k_pr_reset(int32_t T, int64_t cap, int32_t N, float* pref, float* c_t, unsigned long long* hk, KCnt* cr, int32_t* flag,
-                           double* scal) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// every per-call word of the kinds and the preference cleared (thread i: word i of each buffer)
+__device__ __forceinline__ void pr_reset_body(int64_t i, int32_t T, int64_t cap, float* pref, float* c_t,
+                                              unsigned long long* hk, KCnt* cr, int32_t* flag, double* scal) {
     if (i < T) {
         pref[i] = 0.0f;
         c_t[i] = 0.0f;
@@ -58,6 +58,10 @@ __global__ void k_pr_reset(int32_t T, int64_t cap, int32_t N, float* pref, float
     }
     if (i < 8) flag[i] = 0;
     if (i < 8) scal[i] = 0.0;
+}
+__global__ void k_pr_reset(int32_t T, int64_t cap, int32_t N, float* pref, float* c_t, unsigned long long* hk, KCnt* cr, int32_t* flag,
+                           double* scal) {
+    pr_reset_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, T, cap, pref, c_t, hk, cr, flag, scal);
 }
 
 // ---------------------------------------------------------------- graph constants
@@ -926,9 +930,9 @@ __global__ void __launch_bounds__(KB) k_kind_insert(const int64_t* off, const in
 }
 
 template <typename ID>   // int32 ids, or their u16 copy (rs16)
-__global__ void k_kind_verify(const int64_t* off, const ID* ops, const float* w_t, int32_t T,
-                              const KCnt* cr, const int32_t* slot_of, double* kind, int32_t* flag, int32_t* krep) {
-    int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void kind_verify_body(int32_t t, const int64_t* off, const ID* ops, const float* w_t, int32_t T,
+                                                 const KCnt* cr, const int32_t* slot_of, double* kind, int32_t* flag,
+                                                 int32_t* krep) {
     if (t >= T) return;
     const KCnt ks = cr[slot_of[t]];
     const int32_t r = ks.rep;
@@ -940,6 +944,11 @@ __global__ void k_kind_verify(const int64_t* off, const ID* ops, const float* w_
     if (eq && a1 > a0) eq = __float_as_uint(w_t[t]) == __float_as_uint(w_t[r]);
     for (int64_t i = 0; eq && i < a1 - a0; ++i) eq = ops[a0 + i] == ops[b0 + i];
     if (!eq) atomicOr(flag, 1);
+}
+template <typename ID>
+__global__ void k_kind_verify(const int64_t* off, const ID* ops, const float* w_t, int32_t T,
+                              const KCnt* cr, const int32_t* slot_of, double* kind, int32_t* flag, int32_t* krep) {
+    kind_verify_body<ID>((int32_t)(blockIdx.x * blockDim.x + threadIdx.x), off, ops, w_t, T, cr, slot_of, kind, flag, krep);
 }
 
 // Kinds by partition (graphs on one rank), no global hash table:
@@ -1283,11 +1292,21 @@ __global__ void k_kc_tile_mult(const int32_t* tperm, const double* mult, int32_t
 // ---------------------------------------------------------------- preference (pagerank.py:68-85)
 // sums over pr_trace entries: [0] sum 1/k, [1] sum 1/len; block partials then one fixed-order pass
 // mult (kind-compressed graphs): trace i stands for mult[i] traces of its kind
-__global__ void k_pref_partial(const double* kind, const int32_t* pr_trace, const int32_t* pr_len,
-                               const int32_t* len_t, int32_t n_pr, const double* mult, double* part, int32_t* flag) {
+// the block's two sums, in block_sum order, into part[2 blk], part[2 blk + 1]
+__device__ __forceinline__ void pref_partial_store(int32_t blk, double a, double b, double* part) {
     __shared__ double red[TB / WAVE];
+    a = block_sum(a, red);
+    b = block_sum(b, red);
+    if (threadIdx.x == 0) {
+        part[2 * blk] = a;
+        part[2 * blk + 1] = b;
+    }
+}
+__device__ __forceinline__ void pref_partial_body(int32_t blk, const double* kind, const int32_t* pr_trace,
+                                                  const int32_t* pr_len, const int32_t* len_t, int32_t n_pr,
+                                                  const double* mult, double* part, int32_t* flag) {
     double a = 0.0, b = 0.0;
-    int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t i = blk * blockDim.x + threadIdx.x;
     if (i < n_pr) {
         int32_t t = pr_trace ? pr_trace[i] : i;
         int32_t ln = pr_len ? pr_len[i] : len_t[t];
@@ -1299,17 +1318,17 @@ __global__ void k_pref_partial(const double* kind, const int32_t* pr_trace, cons
             b *= mult[t];
         }
     }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = a;
-        part[2 * blockIdx.x + 1] = b;
-    }
+    pref_partial_store(blk, a, b, part);
+}
+__global__ void k_pref_partial(const double* kind, const int32_t* pr_trace, const int32_t* pr_len,
+                               const int32_t* len_t, int32_t n_pr, const double* mult, double* part, int32_t* flag) {
+    pref_partial_body((int32_t)blockIdx.x, kind, pr_trace, pr_len, len_t, n_pr, mult, part, flag);
 }
 
 // (a last-block total inside k_pref_partial was measured slower: the per-block release fence
 // writes back the XCD's L2, 21 us against 6.7 + 5.6 us for the two launches)
-__global__ void k_pref_total(const double* part, int32_t nb, double* scal) {
+// one block of 1024 threads: the nb block partials, strided, then block_sum
+__device__ __forceinline__ void pref_total_body(const double* part, int32_t nb, double* scal) {
     __shared__ double red[1024 / WAVE];
     double a = 0.0, b = 0.0;
     for (int32_t i = threadIdx.x; i < nb; i += blockDim.x) {
@@ -1323,6 +1342,7 @@ __global__ void k_pref_total(const double* part, int32_t nb, double* scal) {
         scal[3] = b;
     }
 }
+__global__ void k_pref_total(const double* part, int32_t nb, double* scal) { pref_total_body(part, nb, scal); }
 
 // reference order, one thread (MR_PR_EXACT_SUMS, T7)
 __global__ void k_pref_total_exact(const double* kind, const int32_t* pr_trace, const int32_t* pr_len,
@@ -1339,6 +1359,12 @@ __global__ void k_pref_total_exact(const double* kind, const int32_t* pr_trace, 
     scal[3] = b;
 }
 
+// the preference of a trace of kind size k and ln spans (scal[2] = sum 1/k, scal[3] = sum 1/len)
+__device__ __forceinline__ double pref_value(double k, int32_t ln, const double* scal, int anomaly, double phi) {
+    return !anomaly ? 1.0 / k / scal[2]                                               // :74
+                    : 1.0 / (k / scal[2] * phi + 1.0 / (double)ln) / scal[3] * phi;   // :80-85 (phi = 0.5)
+}
+
 // tperm (k_tr_a graphs with pr_trace = operation_trace): thread i is position i, and c_t goes to
 // c_tp[i] too (formerly k_tr_gather)
 __global__ void k_pref_apply(const double* kind, const int32_t* pr_trace, const int32_t* pr_len,
@@ -1348,14 +1374,7 @@ __global__ void k_pref_apply(const double* kind, const int32_t* pr_trace, const 
     if (i >= n_pr) return;
     int32_t t = tperm ? tperm[i] : pr_trace ? pr_trace[i] : i;
     int32_t ln = pr_len ? pr_len[i] : len_t[t];
-    double k = kind[t];
-    double v;
-    if (!anomaly) {
-        v = 1.0 / k / scal[2];                                               // :74
-    } else {
-        v = 1.0 / (k / scal[2] * phi + 1.0 / (double)ln) / scal[3] * phi;   // :80-85 (phi = 0.5)
-    }
-    float vf = (float)v;
+    float vf = (float)pref_value(kind[t], ln, scal, anomaly, phi);
     pref[t] = vf;
     c_t[t] = cd * vf;   // (1.0 - d) * v: float32 array times a Python float stays float32 (T4)
     if (tperm) c_tp[i] = cd * vf;
@@ -1365,18 +1384,23 @@ __global__ void k_pref_apply(const double* kind, const int32_t* pr_trace, const 
 // len_t[t] read and pref[t] written coalesced, only c_tp scattered (through tpos, the inverse of
 // tperm).  The position-order form above gathers kind / len_t and scatters pref / c_t at random
 // t: four random streams per trace, 11 ms at C5's 100M traces.  c_t itself
-// is not written: the fused iteration reads only c_tp.
+// is not written: the fused iteration reads only c_tp (the batched set-up passes c_t and has it).
+__device__ __forceinline__ void pref_apply_t_body(int32_t t, const double* __restrict__ kind,
+                                                  const int32_t* __restrict__ len_t, int32_t T,
+                                                  const double* __restrict__ scal, int anomaly, float cd, double phi,
+                                                  float* __restrict__ pref, const int32_t* __restrict__ tpos,
+                                                  float* __restrict__ c_tp, float* __restrict__ c_t) {
+    if (t >= T) return;
+    const float vf = (float)pref_value(kind[t], len_t[t], scal, anomaly, phi);
+    pref[t] = vf;
+    if (c_t) c_t[t] = cd * vf;
+    c_tp[tpos[t]] = cd * vf;   // (1.0 - d) * v in float32 (T4)
+}
 __global__ void k_pref_apply_t(const double* __restrict__ kind, const int32_t* __restrict__ len_t, int32_t T,
                                const double* __restrict__ scal, int anomaly, float cd, double phi, float* __restrict__ pref,
                                const int32_t* __restrict__ tpos, float* __restrict__ c_tp) {
-    const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const double k = kind[t];
-    const double v = !anomaly ? 1.0 / k / scal[2]                                               // :74
-                              : 1.0 / (k / scal[2] * phi + 1.0 / (double)len_t[t]) / scal[3] * phi;   // :80-85
-    const float vf = (float)v;
-    pref[t] = vf;
-    c_tp[tpos[t]] = cd * vf;   // (1.0 - d) * v in float32 (T4)
+    pref_apply_t_body((int32_t)(blockIdx.x * blockDim.x + threadIdx.x), kind, len_t, T, scal, anomaly, cd, phi, pref, tpos,
+                      c_tp, nullptr);
 }
 __global__ void k_inv_perm(const int32_t* __restrict__ perm, int32_t n, int32_t* __restrict__ inv) {
     const int32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1396,6 +1420,42 @@ __device__ __forceinline__ unsigned long long d2bits(double v) {
 
 constexpr int TR_PAD = WAVE;   // k_tr_a's pad ids N .. N + 63 (su = 0)
 __device__ __forceinline__ int32_t cdiv_d(int32_t a, int32_t b) { return (a + b - 1) / b; }
+// The iteration state (thread i: word i of each buffer); v0 = 1 / (N + traces of the whole graph,
+// all shards), pagerank.py:118-119.
+// perm (relabelled fused graphs): su is kept in the kernel's op labels, su[new] = u_o[perm[new]] s
+// w_t: in position order for k_tr_a (w_tp: q is then indexed by position), else by trace
+// su32 (fp32 wide graphs): su also as floats in suf0 / suf1
+__device__ __forceinline__ void iter_init_body(int64_t i, int32_t N, int32_t T, double v0, const float* w_t,
+                                               const double* mw, const float* u_o, const int32_t* perm, double* sp0,
+                                               double* su0, double* su1, double* q64, float* q32, int fp32,
+                                               unsigned long long* mslot, int su32, float* suf0, float* suf1) {
+    if (i < N) {
+        sp0[i] = v0;
+        const double su = (double)u_o[perm ? perm[i] : i] * v0;
+        su0[i] = su32 ? (double)(float)su : su;   // (fp32 wide graphs: k_tr_a's float copies are exact)
+        if (su32) suf0[i] = (float)su;
+    }
+    if (i >= N && i < N + TR_PAD) su0[i] = su1[i] = 0.0;   // the fused walks' pad slots
+    if (su32 && i >= N && i < N + TR_PAD) suf0[i] = suf1[i] = 0.0f;
+    if (i < T) {
+        const double q = (mw ? mw[i] : (double)w_t[i]) * v0;   // mw: w_t times the kind's multiplicity
+        if (fp32) q32[i] = (float)q; else q64[i] = q;
+    }
+    // M_s(0) = M_r(0) = 1: s_0, r_0 are used as they are; slots 1, 2 start cleared
+    if (i < MSLOT_WORDS) mslot[i] = i < 2 * MSH ? d2bits(1.0) : 0ull;
+}
+// pr_reset_body and iter_init_body in one launch (the iteration state depends on nothing the kinds
+// or the preference compute); T_all: traces of the whole graph (all shards)
+__global__ void k_pr_reset_init(int32_t T, int64_t cap, int32_t N, float* pref, float* c_t, unsigned long long* hk,
+                                KCnt* cr, int32_t* flag, double* scal, const float* w_t, const double* mw,
+                                const float* u_o, int64_t T_all, double* sp0, double* su0, double* su1, double* q64,
+                                float* q32, int fp32, unsigned long long* mslot, const int32_t* perm, int su32,
+                                float* suf0, float* suf1) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    pr_reset_body(i, T, cap, pref, c_t, hk, cr, flag, scal);
+    iter_init_body(i, N, T, 1.0 / (double)((int64_t)N + T_all), w_t, mw, u_o, perm, sp0, su0, su1, q64, q32, fp32, mslot,
+                   su32, suf0, suf1);
+}
 // ---------------------------------------------------------------- batched set-up
 // The set-up of many window graphs (reset + iteration state, kinds, preference) as ONE launch per
 // step for all of them (a block range per graph, as the iteration's launches are), instead of six
@@ -1434,28 +1494,10 @@ __device__ __forceinline__ int32_t sd_graph(const SDev* sd, int32_t ng, int32_t 
 __global__ void k_reset_init_b(const SDev* __restrict__ sd, int32_t ng) {
     const SDev& G = sd[sd_graph(sd, ng, (int32_t)blockIdx.x, 0)];
     const int64_t i = (int64_t)((int32_t)blockIdx.x - G.b_reset) * blockDim.x + threadIdx.x;
-    const int32_t T = G.T, N = G.N;
-    if (i < T) {
-        G.pref[i] = 0.0f;
-        G.c_t[i] = 0.0f;
-    }
-    if (i < G.cap) {
-        G.hk[i] = 0ull;
-        G.cr[i] = KCnt{0u, 0x7fffffff};
-    }
-    if (i < 8) G.flag[i] = 0;
-    if (i < 8) G.scal[i] = 0.0;
-    const double v0 = 1.0 / (double)((int64_t)N + G.T_all);      // pagerank.py:118-119
-    if (i < N) {
-        G.sp0[i] = v0;
-        G.su0[i] = (double)G.u_o[G.perm ? G.perm[i] : i] * v0;
-    }
-    if (i >= N && i < N + TR_PAD) G.su0[i] = G.su1[i] = 0.0;
-    if (i < T) {
-        const double q = (double)G.w_tq[i] * v0;
-        if (G.fp32) G.q32[i] = (float)q; else G.q64[i] = q;
-    }
-    if (i < MSLOT_WORDS) G.mslot[i] = i < 2 * MSH ? d2bits(1.0) : 0ull;
+    pr_reset_body(i, G.T, G.cap, G.pref, G.c_t, G.hk, G.cr, G.flag, G.scal);
+    // (no wide graphs here, setup_batchable: no float copies of su)
+    iter_init_body(i, G.N, G.T, 1.0 / (double)((int64_t)G.N + G.T_all), G.w_tq, nullptr, G.u_o, G.perm, G.sp0, G.su0,
+                   G.su1, G.q64, G.q32, G.fp32, G.mslot, 0, nullptr, nullptr);
 }
 __global__ void __launch_bounds__(KB) k_kind_insert_b(const SDev* __restrict__ sd, int32_t ng, uint64_t seed,
                                                       uint64_t hmask) {
@@ -1465,68 +1507,23 @@ __global__ void __launch_bounds__(KB) k_kind_insert_b(const SDev* __restrict__ s
 }
 __global__ void k_kind_verify_b(const SDev* __restrict__ sd, int32_t ng) {
     const SDev& G = sd[sd_graph(sd, ng, (int32_t)blockIdx.x, 2)];
-    const int32_t t = ((int32_t)blockIdx.x - G.b_kver) * blockDim.x + threadIdx.x;
-    if (t >= G.T) return;
-    const KCnt ks = G.cr[G.slot_of[t]];
-    const int32_t r = ks.rep;
-    G.kind[t] = (double)ks.cnt;
-    if (r == t) return;
-    const int64_t a0 = G.off[t], a1 = G.off[t + 1], b0 = G.off[r], b1 = G.off[r + 1];
-    bool eq = (a1 - a0) == (b1 - b0);
-    if (eq && a1 > a0) eq = __float_as_uint(G.w_t[t]) == __float_as_uint(G.w_t[r]);
-    for (int64_t i = 0; eq && i < a1 - a0; ++i) eq = G.o16[a0 + i] == G.o16[b0 + i];
-    if (!eq) atomicOr(G.flag, 1);
+    kind_verify_body<uint16_t>(((int32_t)blockIdx.x - G.b_kver) * blockDim.x + threadIdx.x, G.off, G.o16, G.w_t, G.T, G.cr,
+                               G.slot_of, G.kind, G.flag, nullptr);
 }
 __global__ void k_pref_partial_b(const SDev* __restrict__ sd, int32_t ng) {
-    __shared__ double red[TB / WAVE];
     const SDev& G = sd[sd_graph(sd, ng, (int32_t)blockIdx.x, 3)];
-    const int32_t blk = (int32_t)blockIdx.x - G.b_pref;
-    double a = 0.0, b = 0.0;
-    const int32_t i = blk * blockDim.x + threadIdx.x;
-    if (i < G.T) {
-        const int32_t ln = G.len_t[i];
-        a = 1.0 / G.kind[i];
-        if (ln == 0) atomicOr(G.flag + 1, 1);
-        b = ln ? 1.0 / (double)ln : 0.0;
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        G.ppart[2 * blk] = a;
-        G.ppart[2 * blk + 1] = b;
-    }
+    pref_partial_body((int32_t)blockIdx.x - G.b_pref, G.kind, nullptr, nullptr, G.len_t, G.T, nullptr, G.ppart, G.flag);
 }
 __global__ void k_pref_total_b(const SDev* __restrict__ sd) {   // block g: graph g
-    __shared__ double red[1024 / WAVE];
     const SDev& G = sd[blockIdx.x];
-    const int32_t nb = cdiv_d(G.T, TB);
-    double a = 0.0, b = 0.0;
-    for (int32_t i = threadIdx.x; i < nb; i += blockDim.x) {
-        a += G.ppart[2 * i];
-        b += G.ppart[2 * i + 1];
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        G.scal[2] = a;
-        G.scal[3] = b;
-    }
+    pref_total_body(G.ppart, cdiv_d(G.T, TB), G.scal);
 }
 // in trace order (as k_pref_apply_t): the per-trace reads and writes are coalesced, the one
 // scattered store is c_tp at the trace's position (tpos, the inverse of tperm)
 __global__ void k_pref_apply_b(const SDev* __restrict__ sd, int32_t ng) {
     const SDev& G = sd[sd_graph(sd, ng, (int32_t)blockIdx.x, 3)];
-    const int32_t t = ((int32_t)blockIdx.x - G.b_pref) * blockDim.x + threadIdx.x;
-    if (t >= G.T) return;
-    const int32_t i = G.tpos[t];
-    const double k = G.kind[t];
-    double v;
-    if (!G.anomaly) v = 1.0 / k / G.scal[2];                                               // :74
-    else v = 1.0 / (k / G.scal[2] * G.phi + 1.0 / (double)G.len_t[t]) / G.scal[3] * G.phi;   // :80-85
-    const float vf = (float)v;
-    G.pref[t] = vf;
-    G.c_t[t] = G.cd * vf;   // (1.0 - d) * v in float32 (T4)
-    G.c_tp[i] = G.cd * vf;
+    pref_apply_t_body(((int32_t)blockIdx.x - G.b_pref) * blockDim.x + threadIdx.x, G.kind, G.len_t, G.T, G.scal, G.anomaly,
+                      G.cd, G.phi, G.pref, G.tpos, G.c_tp, G.c_t);
 }
 
 // ---------------------------------------------------------------- window graphs in layout order
@@ -1581,7 +1578,6 @@ __global__ void __launch_bounds__(TS_T) k_lo_cs_b(const LDev* __restrict__ ld, i
 // N + lane), ids relabelled; w_t = fp32(1/len_t), the span count and the class size by position;
 // the block's 1/k and 1/len_t sums (pagerank.py:71-78) into ppart
 __global__ void __launch_bounds__(256) k_lo_fill_b(const LDev* __restrict__ ld, int32_t n) {
-    __shared__ double red[256 / WAVE];
     __shared__ uint16_t lnoc[LO_NOC_MAX];   // the code -> node id table (one LDS read per id)
     const LDev& G = ld[ld_graph(ld, n, (int32_t)blockIdx.x, 1)];
     const int32_t blk = (int32_t)blockIdx.x - G.b_fill;
@@ -1643,106 +1639,25 @@ __global__ void __launch_bounds__(256) k_lo_fill_b(const LDev* __restrict__ ld, 
                                                    (unsigned long long)idv[4 * u + 3] << 48;
         }
     }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        G.ppart[2 * blk] = a;
-        G.ppart[2 * blk + 1] = b;
-    }
+    pref_partial_store(blk, a, b, G.ppart);
 }
 __global__ void __launch_bounds__(1024) k_lo_total_b(const LDev* __restrict__ ld) {   // block g: graph g
-    __shared__ double red[1024 / WAVE];
     const LDev& G = ld[blockIdx.x];
-    double a = 0.0, b = 0.0;
-    for (int32_t i = threadIdx.x; i < G.nbp; i += blockDim.x) {
-        a += G.ppart[2 * i];
-        b += G.ppart[2 * i + 1];
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        G.scal[2] = a;
-        G.scal[3] = b;
-    }
+    pref_total_body(G.ppart, G.nbp, G.scal);
 }
-// the preference (pagerank.py:68-85, T4) and the iteration state (k_reset_init_b's) by position
+// the preference (pagerank.py:68-85, T4) and the iteration state (k_reset_init_b's) by position;
+// of the per-call words only flag[0..3] and scal but [2], [3] (k_lo_total_b's sums) are cleared
 __global__ void k_lo_apply_b(const LDev* __restrict__ ld, int32_t n) {
     const LDev& G = ld[ld_graph(ld, n, (int32_t)blockIdx.x, 2)];
     const int64_t i = (int64_t)((int32_t)blockIdx.x - G.b_app) * blockDim.x + threadIdx.x;
-    const int32_t T = G.T, N = G.N;
-    const double v0 = G.v0;
-    if (i < T) {
-        const double k = G.kind[i];
-        double v;
-        if (!G.anomaly) v = 1.0 / k / G.scal[2];                                                    // :74
-        else v = 1.0 / (k / G.scal[2] * G.phi + 1.0 / (double)G.lenp[i]) / G.scal[3] * G.phi;   // :80-85
-        const float vf = (float)v;
+    if (i < G.T) {
+        const float vf = (float)pref_value(G.kind[i], G.lenp[i], G.scal, G.anomaly, G.phi);
         G.c_tp[i] = G.cd * vf;   // (1.0 - d) * v in float32 (T4)
-        const double q = (double)G.w_tp[i] * v0;
-        if (G.fp32) G.q32[i] = (float)q; else G.q64[i] = q;
     }
-    if (i < N) {
-        G.sp0[i] = v0;
-        G.su0[i] = (double)G.u_o[i] * v0;
-    }
-    if (i >= N && i < N + TR_PAD) G.su0[i] = G.su1[i] = 0.0;
-    if (i < MSLOT_WORDS) G.mslot[i] = i < 2 * MSH ? d2bits(1.0) : 0ull;
+    iter_init_body(i, G.N, G.T, G.v0, G.w_tp, nullptr, G.u_o, nullptr, G.sp0, G.su0, G.su1, G.q64, G.q32, G.fp32, G.mslot,
+                   0, nullptr, nullptr);
     if (i < 4) G.flag[i] = 0;
     if (i < 8 && i != 2 && i != 3) G.scal[i] = 0.0;
-}
-
-// T_all: traces of the whole graph (all shards) for the initial value
-// perm (relabelled fused graphs): su is kept in the kernel's op labels, su[new] = u_o[perm[new]] s
-// w_t: in position order for k_tr_a (w_tp: q is then indexed by position), else by trace
-__global__ void k_iter_init(const float* w_t, const double* mw, const float* u_o, int32_t N, int32_t T, int64_t T_all,
-                            double* sp0, double* su0, double* su1, double* q64, float* q32, int fp32,
-                            unsigned long long* mslot, const int32_t* perm) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const double v0 = 1.0 / (double)((int64_t)N + T_all);      // pagerank.py:118-119
-    if (i < N) {
-        sp0[i] = v0;
-        su0[i] = (double)u_o[perm ? perm[i] : i] * v0;
-    }
-    if (i >= N && i < N + TR_PAD) su0[i] = su1[i] = 0.0;   // the fused walks' pad slots
-    if (i < T) {
-        double q = (mw ? mw[i] : (double)w_t[i]) * v0;   // mw: w_t times the kind's multiplicity
-        if (fp32) q32[i] = (float)q; else q64[i] = q;
-    }
-    // M_s(0) = M_r(0) = 1: s_0, r_0 are used as they are; slots 1, 2 start cleared
-    if (i < MSLOT_WORDS) mslot[i] = i < 2 * MSH ? d2bits(1.0) : 0ull;
-}
-// k_pr_reset and k_iter_init in one launch (the iteration state depends on nothing the kinds or
-// the preference compute)
-__global__ void k_pr_reset_init(int32_t T, int64_t cap, int32_t N, float* pref, float* c_t, unsigned long long* hk,
-                                KCnt* cr, int32_t* flag, double* scal, const float* w_t, const double* mw,
-                                const float* u_o, int64_t T_all, double* sp0, double* su0, double* su1, double* q64,
-                                float* q32, int fp32, unsigned long long* mslot, const int32_t* perm, int su32,
-                                float* suf0, float* suf1) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < T) {
-        pref[i] = 0.0f;
-        c_t[i] = 0.0f;
-    }
-    if (i < cap) {
-        hk[i] = 0ull;
-        cr[i] = KCnt{0u, 0x7fffffff};
-    }
-    if (i < 8) flag[i] = 0;
-    if (i < 8) scal[i] = 0.0;
-    const double v0 = 1.0 / (double)((int64_t)N + T_all);      // pagerank.py:118-119
-    if (i < N) {
-        sp0[i] = v0;
-        const double su = (double)u_o[perm ? perm[i] : i] * v0;
-        su0[i] = su32 ? (double)(float)su : su;   // (fp32 wide graphs: k_tr_a's float copies are exact)
-        if (su32) suf0[i] = (float)su;
-    }
-    if (i >= N && i < N + TR_PAD) su0[i] = su1[i] = 0.0;
-    if (su32 && i >= N && i < N + TR_PAD) suf0[i] = suf1[i] = 0.0f;
-    if (i < T) {
-        const double q = (mw ? mw[i] : (double)w_t[i]) * v0;
-        if (fp32) q32[i] = (float)q; else q64[i] = q;
-    }
-    if (i < MSLOT_WORDS) mslot[i] = i < 2 * MSH ? d2bits(1.0) : 0ull;
 }
 
 // Per-graph view for the batched iteration: one k_iter_a / k_iter_b pair per Jacobi iteration
@@ -2033,11 +1948,6 @@ constexpr int FX_NMAX = 16384;
 // (vmcnt only) instead of flat_load, whose lgkmcnt share would make every LDS wait also wait
 // for outstanding HBM loads
 #define GLB __attribute__((address_space(1)))
-__device__ __forceinline__ int64_t rfl64(int64_t v) {   // a wave-uniform value held in VGPRs -> SGPRs
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 template <class T>
@@ -2108,11 +2018,6 @@ struct TrLds {
     }
 };
 
-__device__ __forceinline__ double uni_d(double v) {   // a block-uniform double into SGPRs
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 // Short tiles (tiles of exactly NC chunks, NC <= 8: traces of <= 32 ops), su in LDS: a tile is ONE register
 // set -- its NC id chunks, q, c = (1-d) v, w (EXT & 1: the kind multiplicity's mw instead),
 // the cold half of the sums (EXT & 2), and the chunk offsets of the next two tiles -- loaded
@@ -3225,8 +3130,9 @@ __global__ void __launch_bounds__(WIDE_CT) k_cold_ops(const int64_t* __restrict_
 }
 
 // result = s/max(s) (pagerank.py:126,129); weight = result * sum(result) / N (:93-107)
-__global__ void __launch_bounds__(1024) k_weights(const double* sp, const unsigned long long* mslot, int k3,
-                                                  int32_t N, int exact, double* sn, double* weight, double* scal) {
+// (one block of up to 1024 threads per graph)
+__device__ __forceinline__ void weights_body(const double* sp, const unsigned long long* mslot, int k3, int32_t N,
+                                             int exact, double* sn, double* weight, double* scal) {
     __shared__ double red[1024 / WAVE];
     __shared__ double tot;
     double ms = -__builtin_huge_val();
@@ -3261,49 +3167,13 @@ __global__ void __launch_bounds__(1024) k_weights(const double* sp, const unsign
     for (int32_t o = threadIdx.x; o < N; o += blockDim.x) weight[o] = sn[o] * total / (double)N;
     if (threadIdx.x == 0) scal[4] = total;
 }
-// k_weights for every graph of a batch (block g: graph g) plus a gather of each graph's four error
+// the weights of every graph of a batch (block g: graph g) plus a gather of each graph's four error
 // words into one buffer, so the call's single read-back is one pinned copy
 __global__ void __launch_bounds__(1024) k_weights_batch(const GDev* __restrict__ gs, int iters, int exact,
                                                         int32_t* flags_out) {
     const GDev& G = gs[blockIdx.x];
     if (threadIdx.x < 4) flags_out[4 * blockIdx.x + threadIdx.x] = G.flag[threadIdx.x];
-    __shared__ double red[1024 / WAVE];
-    __shared__ double tot;
-    const double* sp = G.spb[iters & 1];
-    const int k3 = iters % 3;
-    const int32_t N = G.N;
-    double* sn = G.sn;
-    double ms = -__builtin_huge_val();
-    for (int i = threadIdx.x; i < MSH; i += blockDim.x) ms = nmax(ms, bits2d(G.mslot[(size_t)2 * MSH * k3 + i]));
-    const double Ms = block_max(ms, red);
-    double m = -__builtin_huge_val();
-    for (int32_t o = threadIdx.x; o < N; o += blockDim.x) {
-        double v = sp[o] / Ms;
-        sn[o] = v;
-        m = nmax(m, v);
-    }
-    m = block_max(m, red);
-    for (int32_t o = threadIdx.x; o < N; o += blockDim.x) sn[o] = sn[o] / m;
-    __syncthreads();
-    if (exact) {
-        if (threadIdx.x == 0) {
-            double s = 0.0;
-            for (int32_t o = 0; o < N; ++o) s += sn[o];
-            tot = s;
-        }
-        __syncthreads();
-    } else {
-        int32_t per = (N + blockDim.x - 1) / blockDim.x;
-        int32_t a = threadIdx.x * per, b = min(a + per, N);
-        double s = 0.0;
-        for (int32_t o = a; o < b; ++o) s += sn[o];
-        s = block_sum(s, red);
-        if (threadIdx.x == 0) tot = s;
-        __syncthreads();
-    }
-    const double total = tot;
-    for (int32_t o = threadIdx.x; o < N; o += blockDim.x) G.weight[o] = sn[o] * total / (double)N;
-    if (threadIdx.x == 0) G.scal[4] = total;
+    weights_body(G.spb[iters & 1], G.mslot, iters % 3, G.N, exact, G.sn, G.weight, G.scal);
 }
 // ---------------------------------------------------------------- trace-sharded graphs
 // local call edges (child, parent) as sort keys c << nb | p
@@ -4266,6 +4136,55 @@ static int graph_kinds(mr_ctx* ctx, mr_graph* g, bool chk, bool ktab, uint64_t c
 // (plan-independent: a window's graphs are set up on the stream that built them, before the
 // batch's plan exists -- mr_pagerank_presetup)
 static int lo_setup_one(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp32);
+// traces from which the kinds take the partition path; MR_KIND_PART_MIN: test knob (read per call)
+static int64_t kind_part_min() {
+    const char* kpe = getenv("MR_KIND_PART_MIN");
+    return kpe ? (int64_t)atoll(kpe) : KIND_PART_MIN_DEFAULT;
+}
+// blocks of 256 threads that cover every per-call word of a graph (pr_reset_body, iter_init_body)
+static int32_t reset_grid(int32_t T, uint64_t cap, int32_t N) {
+    return (int32_t)cdiv(std::max<int64_t>({(int64_t)T, (int64_t)cap, (int64_t)N + TR_PAD, MSLOT_WORDS, 16}), 256);
+}
+// The buffers of a graph's iteration state and per-call words (all a layout-order graph needs: its
+// kinds and preference partials come from its prepare)
+static int state_alloc(mr_ctx* ctx, mr_graph* g, bool fp32) {
+    const size_t N = (size_t)g->N, T = (size_t)g->T;
+    MR_TRY(g->flag.alloc(ctx, 8));
+    MR_TRY(g->scal.alloc(ctx, 8));
+    MR_TRY(g->mslot.alloc(ctx, MSLOT_WORDS));
+    MR_TRY(g->sn.alloc(ctx, N));
+    MR_TRY(g->spb[0].alloc(ctx, N));
+    MR_TRY(g->spb[1].alloc(ctx, N));
+    for (int i = 0; i < 2; ++i) {
+        MR_TRY(g->sub[i].alloc(ctx, (size_t)N + TR_PAD));   // [N, N + TR_PAD) = 0: the fused walks' pad slots
+        if (fp32 && g->wide) MR_TRY(g->suf[i].alloc(ctx, (size_t)N + TR_PAD));
+        if (fp32) MR_TRY(g->q32[i].alloc(ctx, T + 1));   // [T]: k_tr_a's pad slot
+        else MR_TRY(g->q64[i].alloc(ctx, T + 1));
+    }
+    MR_TRY(g->weight.alloc(ctx, N));
+    if (g->fused) {
+        MR_TRY(g->c_tp.alloc(ctx, std::max<size_t>(T, 1)));
+        MR_TRY(g->fx_ssv.alloc(ctx, N));
+    } else {
+        MR_TRY(g->part.alloc(ctx, (size_t)std::max<int64_t>(g->n_pairs, 1)));
+    }
+    return MR_OK;
+}
+// Every buffer of a graph's set-up: the kinds' and the preference's (the hash table of cap slots
+// when ktab), then the state's
+static int setup_alloc(mr_ctx* ctx, mr_graph* g, bool fp32, bool ktab, uint64_t cap) {
+    const size_t T = (size_t)g->T;
+    MR_TRY(g->kind.alloc(ctx, T));
+    MR_TRY(g->pref.alloc(ctx, T));
+    MR_TRY(g->c_t.alloc(ctx, T));
+    MR_TRY(g->ppart.alloc(ctx, 2 * (size_t)cdiv(g->n_pr > 0 ? g->n_pr : 1, TB)));
+    if (ktab) {
+        MR_TRY(g->ht_key.alloc(ctx, cap));
+        MR_TRY(g->ht_cr.alloc(ctx, cap));
+        MR_TRY(g->slot_of.alloc(ctx, T));
+    }
+    return state_alloc(ctx, g, fp32);
+}
 static int pagerank_setup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp32, uint32_t flags, bool sharded,
                           uint64_t seed, uint64_t hmask) {
     if (g->lo) return lo_setup_one(ctx, g, anomaly, d, fp32);   // (exact kind classes: no seed to vary)
@@ -4277,46 +4196,15 @@ static int pagerank_setup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool 
     const bool chk = sharded && ctx->nranks > 1;
     uint64_t cap = 1;
     while (cap < 2ull * (uint64_t)T) cap <<= 1;
-    const char* kpe = getenv("MR_KIND_PART_MIN");   // test knob (read per call): traces from which the partition path runs
-    const int64_t kp_min = kpe ? (int64_t)atoll(kpe) : KIND_PART_MIN_DEFAULT;
-    const bool ktab = chk || (int64_t)T < kp_min;
+    const bool ktab = chk || (int64_t)T < kind_part_min();
     if (!ktab) cap = 0;
     const int32_t n_pr = g->n_pr;
     const int nbp = cdiv(n_pr > 0 ? n_pr : 1, TB);
-    MR_TRY(g->kind.alloc(ctx, (size_t)T));
-    MR_TRY(g->pref.alloc(ctx, (size_t)T));
-    MR_TRY(g->c_t.alloc(ctx, (size_t)T));
-    MR_TRY(g->flag.alloc(ctx, 8));
-    MR_TRY(g->scal.alloc(ctx, 8));
-    MR_TRY(g->ppart.alloc(ctx, 2 * (size_t)nbp));
-    if (ktab) {
-        MR_TRY(g->ht_key.alloc(ctx, cap));
-        MR_TRY(g->ht_cr.alloc(ctx, cap));
-        MR_TRY(g->slot_of.alloc(ctx, (size_t)T));
-    }
-    MR_TRY(g->mslot.alloc(ctx, MSLOT_WORDS));
-    MR_TRY(g->sn.alloc(ctx, (size_t)N));
-    MR_TRY(g->spb[0].alloc(ctx, (size_t)N));
-    MR_TRY(g->spb[1].alloc(ctx, (size_t)N));
-    MR_TRY(g->sub[0].alloc(ctx, (size_t)N + TR_PAD));   // [N, N + TR_PAD) = 0: the fused walks' pad slots
-    MR_TRY(g->sub[1].alloc(ctx, (size_t)N + TR_PAD));
-    if (fp32 && g->wide) {
-        MR_TRY(g->suf[0].alloc(ctx, (size_t)N + TR_PAD));
-        MR_TRY(g->suf[1].alloc(ctx, (size_t)N + TR_PAD));
-    }
-    MR_TRY(g->weight.alloc(ctx, (size_t)N));
+    MR_TRY(setup_alloc(ctx, g, fp32, ktab, cap));
     const bool tr = g->fused;
-    if (tr) MR_TRY(g->c_tp.alloc(ctx, (size_t)std::max(T, 1)));
-    if (g->fused) MR_TRY(g->fx_ssv.alloc(ctx, (size_t)N));
-    else MR_TRY(g->part.alloc(ctx, (size_t)std::max<int64_t>(g->n_pairs, 1)));
-    for (int i = 0; i < 2; ++i) {
-        if (fp32) MR_TRY(g->q32[i].alloc(ctx, (size_t)T + 1));   // [T]: k_tr_a's pad slot
-        else MR_TRY(g->q64[i].alloc(ctx, (size_t)T + 1));
-    }
     // one launch clears every per-call word (instead of a memset per buffer) and sets the iteration
-    // state up (k_iter_init's part: it depends on nothing the kinds / preference compute)
-    hipLaunchKernelGGL(k_pr_reset_init,
-                       dim3(cdiv(std::max<int64_t>({(int64_t)T, (int64_t)cap, (int64_t)N + TR_PAD, MSLOT_WORDS, 16}), 256)),
+    // state up (it depends on nothing the kinds / preference compute)
+    hipLaunchKernelGGL(k_pr_reset_init, dim3(reset_grid(T, cap, N)),
                        dim3(256), 0, st, T, (int64_t)cap, N, g->pref.p, g->c_t.p, g->ht_key.p, g->ht_cr.p,
                        g->flag.p, g->scal.p, tr ? g->w_tp.p : g->w_t.p, tr ? g->mw_tp.p : nullptr, g->u_o.p,
                        g->T_all > 0 ? g->T_all : (int64_t)T, g->spb[0].p, g->sub[0].p, g->sub[1].p, g->q64[0].p,
@@ -4368,11 +4256,10 @@ static int pagerank_setup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool 
 
 // Can pagerank_setup of g run inside a batched set-up?  The window graphs' case: a whole graph on
 // one rank, kinds through the hash table with u16 ids, pr_trace = operation_trace, k_tr_a layout.
+// Not wide graphs: only pagerank_setup writes their float copies of su (suf).
 static bool setup_batchable(const mr_graph* g, uint32_t flags) {
-    const char* kpe = getenv("MR_KIND_PART_MIN");
-    const int64_t kp_min = kpe ? (int64_t)atoll(kpe) : KIND_PART_MIN_DEFAULT;
-    return g->T > 0 && (int64_t)g->T < kp_min && !g->kinds_given && !g->mult.p && g->rs_is_sr && g->rs16.p &&
-           g->pr_identity && g->n_pr == g->T && g->fused && g->tperm.p && g->w_tp.p && !g->mw_tp.p &&
+    return g->T > 0 && (int64_t)g->T < kind_part_min() && !g->kinds_given && !g->mult.p && g->rs_is_sr && g->rs16.p &&
+           g->pr_identity && g->n_pr == g->T && g->fused && !g->wide && g->tperm.p && g->w_tp.p && !g->mw_tp.p &&
            !(flags & MR_PR_EXACT_SUMS) && g->T_all == 0;
 }
 
@@ -4389,29 +4276,8 @@ static int pagerank_setup_batch(mr_ctx* ctx, mr_graph* const* gs, const int* ano
         const int32_t N = g->N, T = g->T;
         uint64_t cap = 1;
         while (cap < 2ull * (uint64_t)T) cap <<= 1;
-        const int nbp = cdiv(T, TB);
-        MR_TRY(g->kind.alloc(ctx, (size_t)T));
-        MR_TRY(g->pref.alloc(ctx, (size_t)T));
-        MR_TRY(g->c_t.alloc(ctx, (size_t)T));
-        MR_TRY(g->flag.alloc(ctx, 8));
-        MR_TRY(g->scal.alloc(ctx, 8));
-        MR_TRY(g->ppart.alloc(ctx, 2 * (size_t)nbp));
-        MR_TRY(g->ht_key.alloc(ctx, cap));
-        MR_TRY(g->ht_cr.alloc(ctx, cap));
-        MR_TRY(g->slot_of.alloc(ctx, (size_t)T));
-        MR_TRY(g->mslot.alloc(ctx, MSLOT_WORDS));
-        MR_TRY(g->sn.alloc(ctx, (size_t)N));
-        MR_TRY(g->spb[0].alloc(ctx, (size_t)N));
-        MR_TRY(g->spb[1].alloc(ctx, (size_t)N));
-        MR_TRY(g->sub[0].alloc(ctx, (size_t)N + TR_PAD));
-        MR_TRY(g->sub[1].alloc(ctx, (size_t)N + TR_PAD));
-        MR_TRY(g->weight.alloc(ctx, (size_t)N));
-        MR_TRY(g->c_tp.alloc(ctx, (size_t)std::max(T, 1)));
-        MR_TRY(g->fx_ssv.alloc(ctx, (size_t)N));
-        for (int j = 0; j < 2; ++j) {
-            if (fp32) MR_TRY(g->q32[j].alloc(ctx, (size_t)T + 1));
-            else MR_TRY(g->q64[j].alloc(ctx, (size_t)T + 1));
-        }
+        const int nbp = cdiv(T, TB);   // (n_pr = T)
+        MR_TRY(setup_alloc(ctx, g, fp32, true, cap));
         SDev& v = hs[i];
         v.T = T;
         v.N = N;
@@ -4452,7 +4318,7 @@ static int pagerank_setup_batch(mr_ctx* ctx, mr_graph* const* gs, const int* ano
         v.o16 = g->rs16.p;
         v.len_t = g->len_t.p;
         v.b_reset = br;
-        br += cdiv(std::max<int64_t>({(int64_t)T, (int64_t)cap, (int64_t)N + TR_PAD, MSLOT_WORDS, 16}), 256);
+        br += reset_grid(T, cap, N);
         v.b_kins = bk;
         bk += cdiv(T, KB);
         v.b_kver = bv;
@@ -5033,7 +4899,7 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
     hm.mark("loop");
     hipLaunchKernelGGL(k_weights_batch, dim3(ng), dim3(1024), 0, st, dv.p, iters, (int)((flags & MR_PR_EXACT_SUMS) != 0),
                        fl.p);
-    MR_DEBUG_CHECK(ctx, "k_weights");
+    MR_DEBUG_CHECK(ctx, "k_weights_batch");
     MR_TRY_HIP(ctx, hipGetLastError());
     if (coll && ctx->peer_on) MR_TRY(mr_peer_check(ctx, "peer all-reduce"));   // an error, not wrong sums
     // a shard's local collision must make every rank retry: the error words meet in a MAX
@@ -5086,6 +4952,17 @@ static uint64_t kind_seed(int a) {
 // MR_KIND_TEST_COLLIDE: test knob -- the first attempt keeps 2 bits of every key, so distinct
 // kinds collide and the verification + retry path runs
 static uint64_t kind_hmask(int a) { return (a == 0 && getenv("MR_KIND_TEST_COLLIDE") != nullptr) ? 3ull : ~0ull; }
+// g is set up for a call with these arguments (and the first kind-hash seed): that call skips its own
+static void mark_presetup(mr_graph* g, int anomaly, double d, bool fp32, uint32_t flags) {
+    g->pre_ok = true;
+    g->pre_anomaly = anomaly;
+    g->pre_d = d;
+    g->pre_phi = g->phi;
+    g->pre_fp32 = fp32;
+    g->pre_flags = flags;
+    g->pre_seed = kind_seed(0);
+    g->pre_hmask = kind_hmask(0);
+}
 
 // A graph's kinds, preference and iteration state for its next mr_pagerank(_batch) call with
 // these arguments, on THIS context's stream (the one that built it): mr_windows_batch sets up a
@@ -5102,17 +4979,7 @@ int mr_pagerank_presetup_n(mr_ctx* ctx, mr_graph* const* gs, const int* an, int 
     }
     DBuf<SDev> dsd;   // (returns to this context's pool: reused only by later work on this stream)
     MR_TRY(pagerank_setup_batch(ctx, gs, an, n, d, fp32, kind_seed(0), kind_hmask(0), keep, dsd));
-    for (int i = 0; i < n; ++i) {
-        mr_graph* g = gs[i];
-        g->pre_ok = true;
-        g->pre_anomaly = an[i];
-        g->pre_d = d;
-        g->pre_phi = g->phi;
-        g->pre_fp32 = fp32;
-        g->pre_flags = 0;
-        g->pre_seed = kind_seed(0);
-        g->pre_hmask = kind_hmask(0);
-    }
+    for (int i = 0; i < n; ++i) mark_presetup(gs[i], an[i], d, fp32, 0);
     return MR_OK;
 }
 
@@ -5120,14 +4987,7 @@ int mr_pagerank_presetup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, int pr
     const bool fp32 = precision == MR_FP32;
     if (g->N == 0 || g->T == 0) return MR_OK;   // (the call itself raises)
     MR_TRY(pagerank_setup(ctx, g, anomaly, d, fp32, flags, false, kind_seed(0), kind_hmask(0)));
-    g->pre_ok = true;
-    g->pre_anomaly = anomaly;
-    g->pre_d = d;
-    g->pre_phi = g->phi;
-    g->pre_fp32 = fp32;
-    g->pre_flags = flags;
-    g->pre_seed = kind_seed(0);
-    g->pre_hmask = kind_hmask(0);
+    mark_presetup(g, anomaly, d, fp32, flags);
     return MR_OK;
 }
 
@@ -5135,21 +4995,7 @@ int mr_pagerank_presetup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, int pr
 // the iteration state's buffers of a layout-order graph and its LDev set-up fields
 static int lo_state(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp32, LDev& v) {
     const int32_t N = g->N, T = g->T;
-    MR_TRY(g->flag.alloc(ctx, 8));
-    MR_TRY(g->scal.alloc(ctx, 8));
-    MR_TRY(g->mslot.alloc(ctx, MSLOT_WORDS));
-    MR_TRY(g->sn.alloc(ctx, (size_t)N));
-    MR_TRY(g->spb[0].alloc(ctx, (size_t)N));
-    MR_TRY(g->spb[1].alloc(ctx, (size_t)N));
-    MR_TRY(g->sub[0].alloc(ctx, (size_t)N + TR_PAD));
-    MR_TRY(g->sub[1].alloc(ctx, (size_t)N + TR_PAD));
-    MR_TRY(g->weight.alloc(ctx, (size_t)N));
-    MR_TRY(g->fx_ssv.alloc(ctx, (size_t)N));
-    MR_TRY(g->c_tp.alloc(ctx, (size_t)std::max(T, 1)));
-    for (int j = 0; j < 2; ++j) {
-        if (fp32) MR_TRY(g->q32[j].alloc(ctx, (size_t)T + 1));   // [T]: k_tr_a's pad slot
-        else MR_TRY(g->q64[j].alloc(ctx, (size_t)T + 1));
-    }
+    MR_TRY(state_alloc(ctx, g, fp32));   // (fused, not wide: mr_lo_prepare_batch)
     v.T = T;
     v.N = N;
     v.anomaly = anomaly;
@@ -5174,16 +5020,6 @@ static int lo_state(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp32, 
     v.u_o = g->u_o.p;
     return MR_OK;
 }
-static void lo_mark_presetup(mr_graph* g, int anomaly, double d, bool fp32) {
-    g->pre_ok = true;
-    g->pre_anomaly = anomaly;
-    g->pre_d = d;
-    g->pre_phi = g->phi;
-    g->pre_fp32 = fp32;
-    g->pre_flags = 0;
-    g->pre_seed = kind_seed(0);
-    g->pre_hmask = kind_hmask(0);
-}
 // pagerank_setup of a layout-order graph (a call that did not take its presetup: a group rerun):
 // its kind class sizes, span counts and preference partials by position are kept on the graph
 static int lo_setup_one(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp32) {
@@ -5195,8 +5031,7 @@ static int lo_setup_one(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp
     MR_TRY(dl.upload(ctx, &v, 1));
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_lo_total_b, dim3(1), dim3(1024), 0, st, dl.p);
-    const int64_t na = std::max<int64_t>({(int64_t)g->T, (int64_t)g->N + TR_PAD, MSLOT_WORDS, 8});
-    hipLaunchKernelGGL(k_lo_apply_b, dim3(cdiv(na, 256)), dim3(256), 0, st, dl.p, 1);
+    hipLaunchKernelGGL(k_lo_apply_b, dim3(reset_grid(g->T, 0, g->N)), dim3(256), 0, st, dl.p, 1);
     MR_TRY_HIP(ctx, hipGetLastError());
     MR_TRY_HIP(ctx, hipStreamSynchronize(st));   // (the host descriptor leaves scope)
     return MR_OK;
@@ -5271,7 +5106,7 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
         v.b_fill = bfl;
         bfl += g->lo_nbp;
         v.b_app = bap;
-        bap += cdiv(std::max<int64_t>({(int64_t)T, (int64_t)N + TR_PAD, MSLOT_WORDS, 8}), 256);
+        bap += reset_grid(T, 0, N);   // (no hash table)
         v.pinv = b.pinv.p;
         v.lo_off = sp->lo_off.p;
         v.lo16 = sp->lo16.p;
@@ -5283,7 +5118,7 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
         v.coff = g->coff.p;
         v.tids = g->tids.p;
         v.trun = merge ? g->trun.p : nullptr;
-        lo_mark_presetup(g, anomaly[i], d, fp32);
+        mark_presetup(g, anomaly[i], d, fp32, 0);
     }
     DBuf<LDev> dl;
     MR_TRY(dl.upload(ctx, hv, (size_t)n));
@@ -5340,8 +5175,7 @@ static int kind_compressed_pagerank(mr_ctx* ctx, mr_graph* g, int anomaly, doubl
     // ---- kinds with representatives (the seed sequence of mr_pagerank_batch_impl)
     uint64_t cap = 1;
     while (cap < 2ull * (uint64_t)T) cap <<= 1;
-    const char* kpe = getenv("MR_KIND_PART_MIN");
-    const bool ktab = (int64_t)T < (kpe ? (int64_t)atoll(kpe) : KIND_PART_MIN_DEFAULT);
+    const bool ktab = (int64_t)T < kind_part_min();
     if (!ktab) cap = 0;
     MR_TRY(g->kind.alloc(ctx, (size_t)T));
     MR_TRY(g->krep.alloc(ctx, (size_t)T));
