@@ -3345,6 +3345,12 @@ static int num_cus() {
     return ncu;
 }
 
+// an A/B and test knob that is on unless set to 0 (read per call: tests flip them)
+static inline bool knob_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && atoi(e) == 0);
+}
+
 // ops of the fused kernel's walk: a wide graph's hot ops, else all
 static int32_t kern_n(const mr_graph* g) { return g->wide ? g->NA : g->N; }
 
@@ -3356,7 +3362,7 @@ struct FxPlan {
     bool pf = false;    // window batches: the next launch finishes an iteration (k_tr_a's pf prologue)
     bool w32 = false;   // fp32 wide graphs only: float su and warm labels in LDS (k_tr_a EXT & 8)
 };
-static FxPlan fx_plan(mr_graph* const* gs, int ng) {
+static FxPlan fx_plan(mr_graph* const* gs, int ng, bool fp32, bool sharded) {
     FxPlan P;
     int32_t nmax = 0;
     int64_t tmax = 0;
@@ -3378,6 +3384,29 @@ static FxPlan fx_plan(mr_graph* const* gs, int ng) {
         for (int i = 0; i < ng; ++i)
             if (gs[i]->fused && !gs[i]->relabeled) P.mode = WV_SU_GLOBAL;
     if (P.mode == WV_SU_HOT && TrLds(nmax, WV_SU_HOT).n_hot < 64) P.mode = WV_SU_GLOBAL;
+    // window batches: the next launch's blocks finish an iteration (k_tr_a pf), no k_fx_b between
+    // launches -- every graph fused and plain (no multiplicities, cold sums, merged runs, hot
+    // ops or relabelling), N <= PF_NMAX (three N-word LDS arrays, four blocks per CU).
+    // MR_TR_PF=0 (read per call; A/B and tests): k_fx_b every iteration
+    P.pf = knob_on("MR_TR_PF") && !sharded && ng >= 2 && P.NT == 512 && P.mode == WV_SU_ALL;
+    for (int i = 0; i < ng && P.pf; ++i) {
+        const mr_graph* g = gs[i];
+        P.pf = g->fused && !g->wide && !g->relabeled && !g->nhr && !g->mw_tp.p && kern_n(g) <= PF_NMAX &&
+               !(g->lo && g->lo_merged == 1);
+    }
+    // fp32 wide graphs: su as floats in k_tr_a's LDS, the freed half holding the next ~10k
+    // ("warm") labels' su, so their cold entries read LDS instead of L2 (k_tr_a EXT & 8);
+    // every fused graph of the launch wide and plain (no multiplicities)
+#ifndef MR_AB_NO_W32
+    P.w32 = fp32 && P.mode == WV_SU_ALL && !P.pf;
+#endif
+    bool anyf = false;
+    for (int i = 0; i < ng && P.w32; ++i)
+        if (gs[i]->fused) {
+            anyf = true;
+            P.w32 = gs[i]->wide && !gs[i]->mw_tp.p && !gs[i]->trun.p;
+        }
+    P.w32 = P.w32 && anyf;
     return P;
 }
 static int32_t plan_n_hot(int32_t N, const FxPlan& P) {
@@ -3557,10 +3586,6 @@ static std::vector<int64_t> batch_blocks(mr_graph* const* gs, int ng, const FxPl
         if (nb[(size_t)i] < cap[(size_t)i]) q.push({(double)gs[i]->n_wt / (double)nb[(size_t)i], i});
     }
     return nb;
-}
-static int fused_blocks(mr_ctx* ctx, mr_graph* g, const FxPlan& P, int64_t wsum, int64_t* nfa,
-                        std::vector<CutArg>* defer = nullptr, int64_t force_nb = 0) {
-    return tr_split(ctx, g, P, wsum, nfa, defer, force_nb);
 }
 
 // k_tr_a's layout of a fused graph (after w_t and the kernel's ids rs16 / rsp): traces sorted by
@@ -4448,8 +4473,6 @@ static double iter_bytes(const mr_graph* g, bool fp32) {
            3.0 * w * (double)g->N;
 }
 
-// one attempt with kind-hash seed `seed`; *collided reports a 64-bit key collision found by the
-// exact verification (k_kind_verify / k_sh_kind_check), after which the caller retries
 // MR_PR_HOST_TIMING: host wall time of pagerank_attempt's phases (no syncs added; diagnostics only)
 struct HostMarks {
     bool on = getenv("MR_PR_HOST_TIMING") != nullptr;
@@ -4467,7 +4490,8 @@ struct HostMarks {
         fprintf(stderr, " us\n");
     }
 };
-struct PrAsync {   // (mr_internal.h) what an enqueued batch's kernels still read, and its error words
+// (mr_internal.h) what an enqueued batch's kernels still read, and its error words
+struct PrAsync {
     std::vector<unsigned char> setup_h;
     DBuf<SDev> setup_d;
     std::vector<GDev> hv;
@@ -4483,11 +4507,11 @@ struct PrAsync {   // (mr_internal.h) what an enqueued batch's kernels still rea
         if (ev) (void)hipEventDestroy(ev);
     }
 };
-static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
-                            int iters, int precision, uint32_t flags, bool sharded, uint64_t seed, uint64_t hmask,
-                            bool* collided, PrAsync* as = nullptr) {
-    *collided = false;
-    HostMarks hm(ng);
+
+// ---- the steps of one attempt, in pagerank_attempt's order
+
+// the arguments, before any device work
+static int attempt_check(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, int iters, bool sharded) {
     if (!ctx || ng <= 0 || !gs || !anomaly) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank: bad arguments");
     if (iters < 0) return mr_fail(ctx, MR_ERR_ARG, "iters < 0");
     for (int i = 0; i < ng; ++i) {
@@ -4498,256 +4522,255 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
         if (gs[i]->N == 0 || T == 0)
             return mr_fail(ctx, MR_ERR_VALUE, "zero-size array to reduction operation maximum which has no identity");
     }
-    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const bool fp32 = precision == MR_FP32;
-    FxPlan plan = fx_plan(gs, ng);
-    std::vector<unsigned char> setup_h;   // (batched set-up descriptors: alive until the call's final sync)
-    DBuf<SDev> setup_d;
-    {   // set-up of every graph not set up ahead (mr_pagerank_presetup): batched when they allow it
-        std::vector<mr_graph*> need;
-        std::vector<int> need_a;
-        bool batch = !sharded && getenv("MR_NO_SETUP_BATCH") == nullptr;
-        for (int i = 0; i < ng; ++i) {
-            mr_graph* g = gs[i];
-            const bool pre = g->pre_ok && g->pre_anomaly == anomaly[i] && g->pre_d == d && g->pre_phi == g->phi && g->pre_fp32 == fp32 &&
-                             g->pre_flags == flags && g->pre_seed == seed && g->pre_hmask == hmask && !sharded;
-            g->pre_ok = false;   // the iteration state is consumed by this call
-            if (pre) continue;
-            need.push_back(g);
-            need_a.push_back(anomaly[i]);
-            batch = batch && setup_batchable(g, flags);
-        }
-        if (batch && need.size() >= 2) {
-            MR_TRY(pagerank_setup_batch(ctx, need.data(), need_a.data(), (int)need.size(), d, fp32, seed, hmask,
-                                        setup_h, setup_d));
-        } else {
-            for (size_t j = 0; j < need.size(); ++j)
-                MR_TRY(pagerank_setup(ctx, need[j], need_a[j], d, fp32, flags, sharded, seed, hmask));
-        }
+    return MR_OK;
+}
+
+// set-up of every graph not set up ahead (mr_pagerank_presetup): batched when they allow it
+// setup_h / setup_d: the batched set-up's descriptors, alive until the call's final sync
+static int attempt_setup(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, bool fp32,
+                         uint32_t flags, bool sharded, uint64_t seed, uint64_t hmask,
+                         std::vector<unsigned char>& setup_h, DBuf<SDev>& setup_d) {
+    std::vector<mr_graph*> need;
+    std::vector<int> need_a;
+    bool batch = !sharded && getenv("MR_NO_SETUP_BATCH") == nullptr;
+    for (int i = 0; i < ng; ++i) {
+        mr_graph* g = gs[i];
+        const bool pre = g->pre_ok && g->pre_anomaly == anomaly[i] && g->pre_d == d && g->pre_phi == g->phi && g->pre_fp32 == fp32 &&
+                         g->pre_flags == flags && g->pre_seed == seed && g->pre_hmask == hmask && !sharded;
+        g->pre_ok = false;   // the iteration state is consumed by this call
+        if (pre) continue;
+        need.push_back(g);
+        need_a.push_back(anomaly[i]);
+        batch = batch && setup_batchable(g, flags);
     }
-    hm.mark("setup");
-    {   // window batches: the next launch's blocks finish an iteration (k_tr_a pf), no k_fx_b between
-        // launches -- every graph fused and plain (no multiplicities, cold sums, merged runs, hot
-        // ops or relabelling), N <= PF_NMAX (three N-word LDS arrays, four blocks per CU).
-        // MR_TR_PF=0 (read per call; A/B and tests): k_fx_b every iteration
-        const char* pe = getenv("MR_TR_PF");
-        plan.pf = !(pe && atoi(pe) == 0) && !sharded && ng >= 2 && plan.NT == 512 && plan.mode == WV_SU_ALL;
-        for (int i = 0; i < ng && plan.pf; ++i) {
-            const mr_graph* g = gs[i];
-            plan.pf = g->fused && !g->wide && !g->relabeled && !g->nhr && !g->mw_tp.p && kern_n(g) <= PF_NMAX &&
-                      !(g->lo && g->lo_merged == 1);
-        }
-    }
-    {   // fp32 wide graphs: su as floats in k_tr_a's LDS, the freed half holding the next ~10k
-        // ("warm") labels' su, so their cold entries read LDS instead of L2 (k_tr_a EXT & 8);
-        // every fused graph of the launch wide and plain (no multiplicities)
-#ifndef MR_AB_NO_W32
-        plan.w32 = fp32 && plan.mode == WV_SU_ALL && !plan.pf;
-#endif
-        bool anyf = false;
-        for (int i = 0; i < ng && plan.w32; ++i)
-            if (gs[i]->fused) {
-                anyf = true;
-                plan.w32 = gs[i]->wide && !gs[i]->mw_tp.p && !gs[i]->trun.p;
-            }
-        plan.w32 = plan.w32 && anyf;
-    }
+    if (batch && need.size() >= 2)
+        return pagerank_setup_batch(ctx, need.data(), need_a.data(), (int)need.size(), d, fp32, seed, hmask, setup_h,
+                                    setup_d);
+    for (size_t j = 0; j < need.size(); ++j)
+        MR_TRY(pagerank_setup(ctx, need[j], need_a[j], d, fp32, flags, sharded, seed, hmask));
+    return MR_OK;
+}
+
+// The k_tr_a blocks of every graph (nfa[i]; 0 for a graph off the fused path): ONE tr_split per fused
+// graph, its partial rows allocated, and the launch's per-wave cuts in batches (k_tr_cut_b).
+static int cut_blocks(mr_ctx* ctx, mr_graph* const* gs, int ng, const FxPlan& plan, HostMarks& hm,
+                      std::vector<int64_t>& nfa) {
     int64_t wsum = 0;   // wave tiles of the launch's fused graphs (k_tr_a's block budget)
     for (int i = 0; i < ng; ++i)
         if (gs[i]->fused) wsum += gs[i]->n_wt;
     std::vector<CutArg> cuts;   // the graphs' per-wave cuts, launched together
-    const std::vector<int64_t> nbs = batch_blocks(gs, ng, plan, wsum);
+    // a batch's forced block counts, each replaced by its graph's blocks as tr_split returns them
+    // (empty: the single-graph rule, force 0)
+    nfa = batch_blocks(gs, ng, plan, wsum);
+    if (nfa.empty()) nfa.assign((size_t)ng, 0);
     for (int i = 0; i < ng; ++i) {
         mr_graph* g = gs[i];
-        if (g->fused) {   // the plan's blocks: partial rows and (k_tr_a) the per-wave cut
-            int64_t nfa = 0;
-            MR_TRY(fused_blocks(ctx, g, plan, wsum, &nfa, &cuts, nbs.empty() ? 0 : nbs[(size_t)i]));
-            // (pf: rows and call-graph terms double-buffered, iteration it & 1)
-            MR_TRY(g->fx_part.alloc(ctx, (size_t)(plan.pf ? 2 : 1) * std::max<int64_t>(nfa, 1) * (size_t)kern_n(g)));
-            if (plan.pf) MR_TRY(g->fx_ssv.alloc(ctx, 2 * (size_t)g->N));
-        }
+        if (!g->fused) continue;
+        int64_t& nb = nfa[(size_t)i];   // the plan's blocks: partial rows and (k_tr_a) the per-wave cut
+        MR_TRY(tr_split(ctx, g, plan, wsum, &nb, &cuts, nb));
+        // (pf: rows and call-graph terms double-buffered, iteration it & 1)
+        MR_TRY(g->fx_part.alloc(ctx, (size_t)(plan.pf ? 2 : 1) * std::max<int64_t>(nb, 1) * (size_t)kern_n(g)));
+        if (plan.pf) MR_TRY(g->fx_ssv.alloc(ctx, 2 * (size_t)g->N));
     }
     hm.mark("blocks");
     for (size_t c0 = 0; c0 < cuts.size(); c0 += TC_BATCH) {
         CutBatch cb;
         const size_t n = std::min<size_t>(TC_BATCH, cuts.size() - c0);
         for (size_t j = 0; j < n; ++j) cb.a[j] = cuts[c0 + j];
-        hipLaunchKernelGGL(k_tr_cut_b, dim3((unsigned)n), dim3(TC_T), 0, st, cb);
+        hipLaunchKernelGGL(k_tr_cut_b, dim3((unsigned)n), dim3(TC_T), 0, ctx->stream, cb);
         MR_TRY_HIP(ctx, hipGetLastError());
     }
-    // a sharded wide graph: the widest cold slice span over the ranks (one scale for every rank)
-    uint64_t cold_span_all = 1;
+    return MR_OK;
+}
+
+// a sharded wide graph: the widest cold slice span over the ranks (one scale for every rank)
+static int cold_span_over_ranks(mr_ctx* ctx, mr_graph* const* gs, int ng, bool sharded, uint64_t* cold_span_all) {
+    *cold_span_all = 1;
     for (int i = 0; i < ng; ++i)
-        if (gs[i]->wide) cold_span_all = std::max(cold_span_all, gs[i]->cold_span);
+        if (gs[i]->wide) *cold_span_all = std::max(*cold_span_all, gs[i]->cold_span);
     if (sharded && mr_coll_ready(ctx)) {
         DBuf<uint64_t> csp;
-        MR_TRY(csp.upload(ctx, &cold_span_all, 1));
+        MR_TRY(csp.upload(ctx, cold_span_all, 1));
         MR_TRY(mr_coll_allreduce(ctx, csp.p, 1, MR_DT_U64, 1));
-        MR_TRY(csp.download(ctx, &cold_span_all, 1));
-        MR_TRY_HIP(ctx, hipStreamSynchronize(st));
+        MR_TRY(csp.download(ctx, cold_span_all, 1));
+        MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    // ---- batched power iteration: one k_iter_a + k_iter_b pair per iteration for every graph
-    std::vector<GDev> hv((size_t)ng);
-    int64_t fb16 = 0;   // k_fx_b blocks of the launch at 16 ops per block
-    for (int i = 0; i < ng; ++i)
-        if (gs[i]->fused) fb16 += cdiv(gs[i]->N, 16);
-    const bool fb_many = fb16 > FB_MANY_BLOCKS;
-    int32_t blocks_a = 0, blocks_b = 0, blocks_fa = 0, blocks_fb = 0;
-    size_t lds = VCAP * sizeof(double), lds_f = 0;
-    const char* lfe = getenv("MR_TR_LASTFIN");   // (A/B and tests, read per call) 0: k_fx_b for every graph
-    const bool lastfin_on = !(lfe && atoi(lfe) == 0);
-    const char* sve = getenv("MR_TR_SSV");   // (A/B and tests, read per call) 0: k_fx_b computes the call-graph terms
-    const bool ssv_on = !(sve && atoi(sve) == 0);
-    const char* lse = getenv("MR_TR_LFSSV");   // (A/B and tests, read per call)
-    const bool lfssv_on = !(lse && atoi(lse) == 0);
-    // (A/B, read per call) 0: plain partial-row stores.  Write-through measured C4 rank 0 of 8: 43.1
-    // vs 44.6 us per iteration, C4 whole: within noise (two repeats each)
-    const char* rwe = getenv("MR_TR_ROW_WT");
-    const bool row_wt_on = !(rwe && atoi(rwe) == 0);
-    double bytes = 0.0;
-    for (int i = 0; i < ng; ++i) {
-        mr_graph* g = gs[i];
-        GDev& v = hv[(size_t)i];
-        v.rs_off = g->rs_off.p;
-        v.rs_ops = g->rs_ops.p;
-        v.rs16 = g->rs16.p;
-        v.rsw = g->relabeled ? g->rsp.p : g->rs16.p;
-        v.perm = g->relabeled ? g->perm.p : nullptr;
-        v.n_hot = plan_n_hot(kern_n(g), plan);
-        v.tids = g->tids.p;
-        v.coff = g->coff.p;
-        v.wtile = g->wtile.p;
-        v.c_tp = g->c_tp.p;
-        v.w_tp = g->w_tp.p;
-        v.mw_tp = g->mw_tp.p;
-        v.hmask = g->nhr ? g->hmask.p : nullptr;
-        v.trun = g->lo && g->lo_merged == 1 ? g->trun.p : nullptr;   // (set at prepare: the ids' rotation follows it)
-        v.ctids = g->wide ? g->ctids.p : nullptr;
-        v.ccoff = g->wide ? g->ccoff.p : nullptr;
-        v.nhr = g->fused ? g->nhr : 0;
-        for (int h = 0; h < 8; ++h) v.hop[h] = g->hop[h];
-        v.c_t = g->c_t.p;
-        v.w_t = g->w_t.p;
-        v.u_o = g->u_o.p;
-        v.pw = g->pw.p;
-        v.ltr = g->tl_ltr.p;
-        v.pr_beg = g->pr_beg.p;
-        v.tile_pr0 = g->tile_pr0.p;
-        v.lp = g->lp.p;
-        v.tile_lp0 = g->tile_lp0.p;
-        v.op_pr_off = g->op_pr_off.p;
-        v.op_pr = g->op_pr.p;
-        v.ss_off = g->ss_off.p;
-        v.ss_par = g->ss_par.p;
-        for (int j = 0; j < 2; ++j) {
-            v.q[j] = fp32 ? (void*)g->q32[j].p : (void*)g->q64[j].p;
-            v.sub[j] = g->sub[j].p;
-            v.suf[j] = g->suf[j].p;
-            v.spb[j] = g->spb[j].p;
-        }
-        v.part = g->part.p;
-        v.mslot = g->mslot.p;
-        v.sn = g->sn.p;
-        v.weight = g->weight.p;
-        v.scal = g->scal.p;
-        v.flag = g->flag.p;
-        v.fx_part = (unsigned long long*)g->fx_part.p;
-        v.fx_ssv = g->fx_ssv.p;
-        v.fx_limb = (unsigned long long*)g->fx_limb.p;
-        v.op_sum = g->op_sum.p;
-        v.rank = ctx->rank;
-        v.nranks = ctx->nranks;
-        // a shard without traces still runs one (empty) block: it clears the maxima slot and
-        // writes a zero partial row, and the collectives after the launch need every rank
-        int64_t nfa = 0;
-        if (g->fused) MR_TRY(fused_blocks(ctx, g, plan, wsum, &nfa, nullptr, nbs.empty() ? 0 : nbs[(size_t)i]));
-        nfa = g->fused ? std::max<int64_t>(nfa, sharded ? 1 : 0) : 0;
-        // a row entry stays below 2^64 (traces per block < 2^(64-sc)).  Shards of one graph hold
-        // different trace counts and their limbs are summed, so they share one scale, 2^48 (<= 65535
-        // traces per block: wv_blocks / fx_blocks); window graphs take their cut-independent scale
-        // (tr_scfix); a graph cut on the device carries its scale there (dscale)
-        const int64_t tpb = g->fused ? g->wtile_msum : 0;
-        const int sc = sharded ? 48 : tr_scfix(g) > 0 ? tr_scfix(g) : 64 - bits_for((uint64_t)std::max<int64_t>(tpb, 1));
-        v.alpha = alpha;
-        v.fx_scale = std::ldexp(1.0, sc);
-        v.fx_iscale = std::ldexp(1.0, -sc);
-        v.T = g->T;
-        v.N = g->N;
-        v.NA = kern_n(g);
-        v.cold_rw = g->cold_rw;
-        v.ns_warm = plan.w32 ? v.NA + std::min(TrLds(v.NA, WV_SU_ALL, false, true).n_warm, g->N - v.NA) : v.NA;
-        v.su32 = fp32 && g->wide;
-        v.cold_acc = g->wide ? g->cold_acc.p : nullptr;
-        v.cold_part = (const unsigned long long*)g->cold_part.p;
-        v.cold_rowbase = g->cold_rowbase.p;
-        v.cx_scale = v.fx_scale;
-        v.cx_iscale = v.fx_iscale;
-        // the graph's scale on the device (k_tr_cut) unless the ranks share the fixed one
-        v.dscale = (!sharded && g->fused && g->wtile_msum < 0) ? g->dscale.p : nullptr;
-        if (g->wide) {
-            // cold rows: at most cold_span adds per op and row; a sharded graph's ranks sum their
-            // limbs per op, and an op hot on one rank may be cold on another: one scale for both
-            // (the smaller), agreed over the ranks (cold_span_all)
-            const int scc = 64 - bits_for(sharded ? cold_span_all : g->cold_span);
-            if (sharded) {
-                const int s1 = std::min(sc, scc);
-                v.fx_scale = v.cx_scale = std::ldexp(1.0, s1);
-                v.fx_iscale = v.cx_iscale = std::ldexp(1.0, -s1);
-            } else {
-                v.cx_scale = std::ldexp(1.0, scc);
-                v.cx_iscale = std::ldexp(1.0, -scc);
-            }
-        }
-        v.blk0f = blocks_fa;
-        v.n_fa = (int32_t)nfa;
-        blocks_fa += v.n_fa;
-        v.blk0fb = blocks_fb;
-        v.fb_ops = fb_ops(g->N, fb_many);
-        // the last k_tr_a block finishes small graphs itself (window batches: one launch per
-        // iteration); its sc1 row reads stay short: at most LASTFIN_WORDS row words
-        // (ops <= threads: the finishing block takes every op in one round -- C3's 500-op windows;
-        // C2's 1000-op windows measured -1.5 % with it, C3 +6.5 % windows/s, -7 % single window)
-        v.lastfin = lastfin_on && plan.NT == 512 && !sharded && g->fused && !g->wide && !g->relabeled &&
-                    plan.mode == WV_SU_ALL && nfa >= 1 && g->N <= plan.NT && nfa * (int64_t)g->N <= LASTFIN_WORDS;
-        v.n_fb = g->fused && !v.lastfin ? cdiv(g->N, v.fb_ops) : 0;
-        // the call-graph terms in k_tr_a (large graphs: k_fx_b's chains of dependent loads leave its
-        // critical path; not for wide graphs: k_fx_b's columns past NA).  Last-block graphs: every
-        // block writes its share write-through and the last block reads the terms with one load per
-        // op instead of the ss_off -> ss_par -> pw / s_k chain (MR_TR_LFSSV=0: the chain; read per call)
-        v.ssv_pre = ssv_on && nfa >= 1 && !g->wide && ((v.n_fb > 0 && g->N >= 2048) || (v.lastfin && lfssv_on));
-        v.pf = plan.pf && !v.lastfin && nfa <= PF_ROWS;
-        v.pf_stride = nfa * (int64_t)kern_n(g);
-        if (v.pf) v.ssv_pre = 1;   // (the next launch's prologue reads the terms: one load per op)
-        v.row_wt = row_wt_on && g->N >= 2048;
-        blocks_fb += v.n_fb;
-        v.blk0 = blocks_a;
-        v.blk0b = blocks_b;
-        bytes += iter_bytes(g, fp32);
-        if (g->fused) {
-            continue;   // no tile-path blocks (n_tb = n_tiles = n_ob = 0)
-        }
-        v.n_tb = std::max(cdiv(g->T, TB), sharded ? 1 : 0);   // (empty shard: see nfa)
-        v.n_tiles = g->n_tiles;
-        v.tshift = g->tshift;
-        v.lds_su = g->N <= LDS_NODES;
-        blocks_a += v.n_tb + v.n_tiles;
-        v.n_ob = cdiv(g->N, TB / WAVE);
-        blocks_b += v.n_ob;
-        if (v.lds_su) lds = std::max(lds, ((size_t)g->N + VCAP) * sizeof(double));
-        lds = std::max(lds, ((size_t)1 << g->tshift) * (fp32 ? sizeof(float) : sizeof(double)));
+    return MR_OK;
+}
+
+// The launch-form knobs (A/B and tests, read once per attempt), each on unless set to 0
+struct TrKnobs {
+    bool lastfin = knob_on("MR_TR_LASTFIN");   // 0: k_fx_b for every graph
+    bool ssv = knob_on("MR_TR_SSV");           // 0: k_fx_b computes the call-graph terms
+    bool lfssv = knob_on("MR_TR_LFSSV");       // 0: last-block graphs read the terms through the chain
+    // 0: plain partial-row stores.  Write-through measured C4 rank 0 of 8: 43.1 vs 44.6 us per
+    // iteration, C4 whole: within noise (two repeats each)
+    bool row_wt = knob_on("MR_TR_ROW_WT");
+};
+
+// What the iteration's launches share: block totals and LDS sizes, summed over the graphs' descriptors
+// (gdev_launch), then the launch's variant and streams (finalise_launch, prepare_exchange)
+struct Launch {
+    int32_t blocks_a = 0, blocks_b = 0, blocks_fa = 0, blocks_fb = 0;   // k_iter_a / k_iter_b / k_tr_a / k_fx_b
+    size_t lds = VCAP * sizeof(double), lds_f = 0;   // k_iter_a's / k_tr_a's LDS bytes
+    double bytes = 0.0;                     // algorithmic bytes of one iteration (profiling)
+    int32_t split_fa = 0, split_fb = 0;     // two graphs: the second one's first block (no search)
+    TrA tr_a = nullptr;                     // the k_tr_a variant
+    bool launch_pf = false;                 // every graph finishes in-kernel: no k_fx_b before the last iteration
+    bool fb_small = false;                  // k_fx_b's block size: 4 waves
+    bool coll = false, any_wide = false, px_on = false;
+    hipStream_t sst = nullptr;              // k_cold_ops' stream (the side stream, or the main one)
+    MrPeerX px{}, px_off{};                 // the peer exchange inside k_fx_b (px_on), and none
+};
+
+// A graph's descriptor, part 1: its arrays and sizes, field for field
+static void gdev_pointers(GDev& v, const mr_ctx* ctx, const mr_graph* g, bool fp32, double alpha, const FxPlan& plan) {
+    v.rs_off = g->rs_off.p;
+    v.rs_ops = g->rs_ops.p;
+    v.rs16 = g->rs16.p;
+    v.rsw = g->relabeled ? g->rsp.p : g->rs16.p;
+    v.perm = g->relabeled ? g->perm.p : nullptr;
+    v.n_hot = plan_n_hot(kern_n(g), plan);
+    v.tids = g->tids.p;
+    v.coff = g->coff.p;
+    v.wtile = g->wtile.p;
+    v.c_tp = g->c_tp.p;
+    v.w_tp = g->w_tp.p;
+    v.mw_tp = g->mw_tp.p;
+    v.hmask = g->nhr ? g->hmask.p : nullptr;
+    v.trun = g->lo && g->lo_merged == 1 ? g->trun.p : nullptr;   // (set at prepare: the ids' rotation follows it)
+    v.ctids = g->wide ? g->ctids.p : nullptr;
+    v.ccoff = g->wide ? g->ccoff.p : nullptr;
+    v.nhr = g->fused ? g->nhr : 0;
+    for (int h = 0; h < 8; ++h) v.hop[h] = g->hop[h];
+    v.c_t = g->c_t.p;
+    v.w_t = g->w_t.p;
+    v.u_o = g->u_o.p;
+    v.pw = g->pw.p;
+    v.ltr = g->tl_ltr.p;
+    v.pr_beg = g->pr_beg.p;
+    v.tile_pr0 = g->tile_pr0.p;
+    v.lp = g->lp.p;
+    v.tile_lp0 = g->tile_lp0.p;
+    v.op_pr_off = g->op_pr_off.p;
+    v.op_pr = g->op_pr.p;
+    v.ss_off = g->ss_off.p;
+    v.ss_par = g->ss_par.p;
+    for (int j = 0; j < 2; ++j) {
+        v.q[j] = fp32 ? (void*)g->q32[j].p : (void*)g->q64[j].p;
+        v.sub[j] = g->sub[j].p;
+        v.suf[j] = g->suf[j].p;
+        v.spb[j] = g->spb[j].p;
     }
-    const int32_t split_fa = ng == 2 ? hv[1].blk0f : 0, split_fb = ng == 2 ? hv[1].blk0fb : 0;
-    for (int i = 0; i < ng; ++i)
-        if (gs[i]->fused) lds_f = std::max(lds_f, plan_lds(kern_n(gs[i]), plan));
-    {   // last-block graphs: a launch that fits one block per CU runs so (LDS past half a CU), and its
-        // finishing blocks skip the acquire (tr_last_finish); else they take it
-        bool any_lf = false;
-        for (int i = 0; i < ng; ++i) any_lf = any_lf || hv[(size_t)i].lastfin;
-        const bool one_cu = LF_ONE_CU_LDS > 0 && any_lf && blocks_fa <= num_cus() && LF_ONE_CU_LDS <= WV_LDS_MAX;
-        if (one_cu) lds_f = std::max(lds_f, LF_ONE_CU_LDS);
-        for (int i = 0; i < ng; ++i) hv[(size_t)i].lf_acq = one_cu ? 0 : 1;
+    v.part = g->part.p;
+    v.mslot = g->mslot.p;
+    v.sn = g->sn.p;
+    v.weight = g->weight.p;
+    v.scal = g->scal.p;
+    v.flag = g->flag.p;
+    v.fx_part = (unsigned long long*)g->fx_part.p;
+    v.fx_ssv = g->fx_ssv.p;
+    v.fx_limb = (unsigned long long*)g->fx_limb.p;
+    v.op_sum = g->op_sum.p;
+    v.rank = ctx->rank;
+    v.nranks = ctx->nranks;
+    v.alpha = alpha;
+    v.T = g->T;
+    v.N = g->N;
+    v.NA = kern_n(g);
+    v.cold_rw = g->cold_rw;
+    v.ns_warm = plan.w32 ? v.NA + std::min(TrLds(v.NA, WV_SU_ALL, false, true).n_warm, g->N - v.NA) : v.NA;
+    v.su32 = fp32 && g->wide;
+    v.cold_acc = g->wide ? g->cold_acc.p : nullptr;
+    v.cold_part = (const unsigned long long*)g->cold_part.p;
+    v.cold_rowbase = g->cold_rowbase.p;
+}
+
+// Part 2: the fixed-point scales of the partial rows (fx_*), of a wide graph's cold rows (cx_*), and
+// the scale a device cut left on the device (dscale)
+static void gdev_scales(GDev& v, const mr_graph* g, bool sharded, uint64_t cold_span_all) {
+    // a row entry stays below 2^64 (traces per block < 2^(64-sc)).  Shards of one graph hold
+    // different trace counts and their limbs are summed, so they share one scale, 2^48 (<= 65535
+    // traces per block: wv_blocks / fx_blocks); window graphs take their cut-independent scale
+    // (tr_scfix); a graph cut on the device carries its scale there (dscale)
+    const int64_t tpb = g->fused ? g->wtile_msum : 0;
+    const int sc = sharded ? 48 : tr_scfix(g) > 0 ? tr_scfix(g) : 64 - bits_for((uint64_t)std::max<int64_t>(tpb, 1));
+    int sf = sc, sx = sc;   // the rows' and the cold rows' scales (2^sf, 2^sx)
+    if (g->wide) {
+        // cold rows: at most cold_span adds per op and row; a sharded graph's ranks sum their
+        // limbs per op, and an op hot on one rank may be cold on another: one scale for both
+        // (the smaller), agreed over the ranks (cold_span_all)
+        sx = 64 - bits_for(sharded ? cold_span_all : g->cold_span);
+        if (sharded) sf = sx = std::min(sc, sx);
     }
+    v.fx_scale = std::ldexp(1.0, sf);
+    v.fx_iscale = std::ldexp(1.0, -sf);
+    v.cx_scale = std::ldexp(1.0, sx);
+    v.cx_iscale = std::ldexp(1.0, -sx);
+    // the graph's scale on the device (k_tr_cut) unless the ranks share the fixed one
+    v.dscale = (!sharded && g->fused && g->wtile_msum < 0) ? g->dscale.p : nullptr;
+}
+
+// Part 3: the graph's blocks in each of the iteration's launches (nfa: its k_tr_a blocks, cut_blocks)
+// and the form its iterations take; the launch's totals grow by them
+static void gdev_launch(GDev& v, const mr_graph* g, int64_t nfa, bool fp32, bool sharded, const FxPlan& plan,
+                        const TrKnobs& kn, bool fb_many, Launch& L) {
+    // a shard without traces still runs one (empty) block: it clears the maxima slot and
+    // writes a zero partial row, and the collectives after the launch need every rank
+    nfa = g->fused ? std::max<int64_t>(nfa, sharded ? 1 : 0) : 0;
+    v.blk0f = L.blocks_fa;
+    v.n_fa = (int32_t)nfa;
+    L.blocks_fa += v.n_fa;
+    v.blk0fb = L.blocks_fb;
+    v.fb_ops = fb_ops(g->N, fb_many);
+    // the last k_tr_a block finishes small graphs itself (window batches: one launch per
+    // iteration); its sc1 row reads stay short: at most LASTFIN_WORDS row words
+    // (ops <= threads: the finishing block takes every op in one round -- C3's 500-op windows;
+    // C2's 1000-op windows measured -1.5 % with it, C3 +6.5 % windows/s, -7 % single window)
+    v.lastfin = kn.lastfin && plan.NT == 512 && !sharded && g->fused && !g->wide && !g->relabeled &&
+                plan.mode == WV_SU_ALL && nfa >= 1 && g->N <= plan.NT && nfa * (int64_t)g->N <= LASTFIN_WORDS;
+    v.n_fb = g->fused && !v.lastfin ? cdiv(g->N, v.fb_ops) : 0;
+    // the call-graph terms in k_tr_a (large graphs: k_fx_b's chains of dependent loads leave its
+    // critical path; not for wide graphs: k_fx_b's columns past NA).  Last-block graphs: every
+    // block writes its share write-through and the last block reads the terms with one load per
+    // op instead of the ss_off -> ss_par -> pw / s_k chain (MR_TR_LFSSV=0: the chain; read per call)
+    v.ssv_pre = kn.ssv && nfa >= 1 && !g->wide && ((v.n_fb > 0 && g->N >= 2048) || (v.lastfin && kn.lfssv));
+    v.pf = plan.pf && !v.lastfin && nfa <= PF_ROWS;
+    v.pf_stride = nfa * (int64_t)kern_n(g);
+    if (v.pf) v.ssv_pre = 1;   // (the next launch's prologue reads the terms: one load per op)
+    v.row_wt = kn.row_wt && g->N >= 2048;
+    L.blocks_fb += v.n_fb;
+    v.blk0 = L.blocks_a;
+    v.blk0b = L.blocks_b;
+    L.bytes += iter_bytes(g, fp32);
+    if (g->fused) {   // no tile-path blocks (n_tb = n_tiles = n_ob = 0)
+        L.lds_f = std::max(L.lds_f, plan_lds(kern_n(g), plan));
+        return;
+    }
+    v.n_tb = std::max(cdiv(g->T, TB), sharded ? 1 : 0);   // (empty shard: see nfa)
+    v.n_tiles = g->n_tiles;
+    v.tshift = g->tshift;
+    v.lds_su = g->N <= LDS_NODES;
+    L.blocks_a += v.n_tb + v.n_tiles;
+    v.n_ob = cdiv(g->N, TB / WAVE);
+    L.blocks_b += v.n_ob;
+    if (v.lds_su) L.lds = std::max(L.lds, ((size_t)g->N + VCAP) * sizeof(double));
+    L.lds = std::max(L.lds, ((size_t)1 << g->tshift) * (fp32 ? sizeof(float) : sizeof(double)));
+}
+
+// The launch's variant, from its graphs' descriptors: the one-CU rule, the k_tr_a kernel, whether every
+// graph finishes in-kernel (launch_pf), k_fx_b's block size.  Rejects the two batches no variant runs.
+static int finalise_launch(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, bool sharded, const FxPlan& plan,
+                           const TrKnobs& kn, std::vector<GDev>& hv, Launch& L) {
+    L.split_fa = ng == 2 ? hv[1].blk0f : 0;
+    L.split_fb = ng == 2 ? hv[1].blk0fb : 0;
+    // last-block graphs: a launch that fits one block per CU runs so (LDS past half a CU), and its
+    // finishing blocks skip the acquire (tr_last_finish); else they take it
+    bool any_lf = false;
+    for (int i = 0; i < ng; ++i) any_lf = any_lf || hv[(size_t)i].lastfin;
+    const bool one_cu = LF_ONE_CU_LDS > 0 && any_lf && L.blocks_fa <= num_cus() && LF_ONE_CU_LDS <= WV_LDS_MAX;
+    if (one_cu) L.lds_f = std::max(L.lds_f, LF_ONE_CU_LDS);
+    for (int i = 0; i < ng; ++i) hv[(size_t)i].lf_acq = one_cu ? 0 : 1;
     for (int i = 0; i < ng; ++i)   // hot-op layouts need every op's su in LDS (a batch with a much wider graph)
         if (gs[i]->fused && gs[i]->nhr && plan.mode != WV_SU_ALL)
             return mr_fail(ctx, MR_ERR_ARG, "pagerank batch: a hot-op layout (T >= MR_TR_HOT_MIN) with a graph of > %d ops",
@@ -4760,63 +4783,74 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
     for (int i = 0; i < ng; ++i)   // the wide variant carries HOT_MAX_WIDE hot accumulators
         if ((any_ext & 2) && gs[i]->fused && gs[i]->nhr > HOT_MAX_WIDE)
             return mr_fail(ctx, MR_ERR_ARG, "pagerank batch: a hot-op layout of %d ops beside a wide graph", gs[i]->nhr);
-    bool launch_pf = plan.pf;   // every graph finishes in-kernel: no k_fx_b before the last iteration
-    for (int i = 0; i < ng; ++i) launch_pf = launch_pf && (hv[(size_t)i].lastfin || hv[(size_t)i].pf);
-    launch_pf = launch_pf && any_ext == 0;
-    if (!launch_pf)
+    L.launch_pf = plan.pf;
+    for (int i = 0; i < ng; ++i) L.launch_pf = L.launch_pf && (hv[(size_t)i].lastfin || hv[(size_t)i].pf);
+    L.launch_pf = L.launch_pf && any_ext == 0;
+    if (!L.launch_pf)
         for (int i = 0; i < ng; ++i) {
-            if (hv[(size_t)i].pf) hv[(size_t)i].ssv_pre = ssv_on && !gs[i]->wide && gs[i]->N >= 2048;
+            if (hv[(size_t)i].pf) hv[(size_t)i].ssv_pre = kn.ssv && !gs[i]->wide && gs[i]->N >= 2048;
             hv[(size_t)i].pf = 0;
         }
-    const TrA tr_a = tr_kernel(fp32, plan.mode, plan.NT, any_ext == 2 && plan.w32 ? 10 : any_ext);
-    DBuf<GDev> dv;
-    hm.mark("descr");
-    MR_TRY(dv.upload(ctx, hv.data(), hv.size()));
+    L.tr_a = tr_kernel(fp32, plan.mode, plan.NT, any_ext == 2 && plan.w32 ? 10 : any_ext);
     // a sharded graph with no collective backend is one whole shard: the split launches around the
     // (no-op) all-reduces would compute the same integers / sums in two halves
-    const bool coll = sharded && mr_coll_ready(ctx);
+    L.coll = sharded && mr_coll_ready(ctx);
+    for (int i = 0; i < ng; ++i) L.any_wide = L.any_wide || gs[i]->wide;
+    // k_fx_b's block size: 4 waves when no graph of the launch has many partial rows
+    L.fb_small = !L.any_wide;
+    // (a large graph alone -- C4: 256 rows of 10k ops -- sums faster with 16-wave blocks: 137 -> 134 us)
+    for (int i = 0; i < ng; ++i)
+        L.fb_small = L.fb_small && hv[(size_t)i].n_fa <= FB_SMALL_ROWS && hv[(size_t)i].N <= 4096;
+    return MR_OK;
+}
+
+// What the launches need beside the descriptors: the side stream of a launch with wide graphs, and a
+// sharded graph's peer exchange
+static int prepare_exchange(mr_ctx* ctx, mr_graph* const* gs, int ng, Launch& L) {
     // wide graphs: k_cold_ops (LDS-bound) runs on the side stream beside k_cold_trace (L2-gather
     // bound) and k_tr_a on the main stream; k_fx_b waits for both
-    bool any_wide = false;
-    for (int i = 0; i < ng; ++i) any_wide = any_wide || gs[i]->wide;
-    // k_fx_b's block size: 4 waves when no graph of the launch has many partial rows
-    bool fb_small = !any_wide;
-    // (a large graph alone -- C4: 256 rows of 10k ops -- sums faster with 16-wave blocks: 137 -> 134 us)
-    for (int i = 0; i < ng; ++i) fb_small = fb_small && hv[(size_t)i].n_fa <= FB_SMALL_ROWS && hv[(size_t)i].N <= 4096;
-    hipStream_t sst = st;
-#ifdef MR_AB_WIDE_SERIAL   // (A/B builds: k_cold_ops on the main stream)
-    if (false) {
-#else
-    if (any_wide) {
-#endif
+    L.sst = ctx->stream;
+#ifndef MR_AB_WIDE_SERIAL   // (A/B builds: k_cold_ops on the main stream)
+    if (L.any_wide) {
         if (!ctx->side) {
             MR_TRY_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
             for (hipEvent_t& e : ctx->side_ev) MR_TRY_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        sst = ctx->side;
+        L.sst = ctx->side;
     }
+#endif
     // sharded fused graph on the peer path: the exchange inside k_fx_b (MR_PEER_SPLIT=1: the separate
     // push / reduce launches; relabelled graphs always -- the ranks' op labels differ, so a block's
     // columns on one rank are not the same ops on another)
-    MrPeerX px{}, px_off{};
-    bool px_on = false;
-    if (coll && ng == 1 && gs[0]->fused && !gs[0]->wide && !gs[0]->relabeled && mr_peer_ready(ctx) &&
+    if (L.coll && ng == 1 && gs[0]->fused && !gs[0]->wide && !gs[0]->relabeled && mr_peer_ready(ctx) &&
         !getenv("MR_PEER_SPLIT")) {
-        const int prc = mr_peer_fx_prepare(ctx, 2 * (int64_t)gs[0]->N + ctx->nranks, (int32_t)blocks_fb, &px);
+        const int prc = mr_peer_fx_prepare(ctx, 2 * (int64_t)gs[0]->N + ctx->nranks, L.blocks_fb, &L.px);
         if (prc == MR_OK) {
-            px_on = true;
+            L.px_on = true;
             // ranks sharing a device: mode-2 blocks spinning there would hold CUs a peer's 160-KB
             // k_tr_a blocks need -- one waiting block instead (MR_PEER_SPIN=0/1 forces it)
             const char* se = getenv("MR_PEER_SPIN");
-            px.spin = se ? atoi(se) != 0 : !mr_peer_same_device(ctx);
+            L.px.spin = se ? atoi(se) != 0 : !mr_peer_same_device(ctx);
         } else if (prc != MR_ERR_STATE) {
             return prc;
         }
     }
-    hm.mark("pre-loop");
+    return MR_OK;
+}
+
+// The power iteration: per iteration the wide graphs' cold halves, k_tr_a + k_fx_b for the fused graphs
+// and k_iter_a + k_iter_b for the others, a sharded graph's all-reduce between each pair's halves
+static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d, double alpha, int iters,
+                   const FxPlan& plan, const std::vector<GDev>& hv, const GDev* dv, Launch& L) {
+    hipStream_t st = ctx->stream, sst = L.sst;
+    const bool side = L.any_wide && sst != st;
+    const auto cold_ops = fp32 ? k_cold_ops<float> : k_cold_ops<double>;
+    const auto iter_a = fp32 ? k_iter_a<float> : k_iter_a<double>;
+    const auto fx_b_k = L.fb_small ? k_fx_b<FB_W_SMALL> : k_fx_b<FB_W>;
+    const int fb_threads = WAVE * (L.fb_small ? FB_W_SMALL : FB_W);
     for (int it = 0; it < iters; ++it) {
         mr_prof_begin(ctx);
-        if (any_wide && sst != st) {
+        if (side) {
             MR_TRY_HIP(ctx, hipEventRecord(ctx->side_ev[0], st));   // this iteration's su and q are ready
             MR_TRY_HIP(ctx, hipStreamWaitEvent(sst, ctx->side_ev[0], 0));
         }
@@ -4825,94 +4859,134 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
             if (!g->wide) continue;
             const void* qc = fp32 ? (const void*)g->q32[it & 1].p : (const void*)g->q64[it & 1].p;
             const size_t lds_c = (size_t)g->cold_rw * sizeof(unsigned long long);
-            if (fp32)
-                hipLaunchKernelGGL(k_cold_ops<float>, dim3(g->n_cb), dim3(WIDE_CT), lds_c, sst, g->cb_beg.p, g->cp_pos.p,
-                                   g->cp_op.p, qc, g->mslot.p, it, hv[(size_t)i].cx_scale, g->cold_rw,
-                                   (unsigned long long*)g->cold_part.p);
-            else
-                hipLaunchKernelGGL(k_cold_ops<double>, dim3(g->n_cb), dim3(WIDE_CT), lds_c, sst, g->cb_beg.p, g->cp_pos.p,
-                                   g->cp_op.p, qc, g->mslot.p, it, hv[(size_t)i].cx_scale, g->cold_rw,
-                                   (unsigned long long*)g->cold_part.p);
+            hipLaunchKernelGGL(cold_ops, dim3(g->n_cb), dim3(WIDE_CT), lds_c, sst, g->cb_beg.p, g->cp_pos.p, g->cp_op.p,
+                               qc, g->mslot.p, it, hv[(size_t)i].cx_scale, g->cold_rw, (unsigned long long*)g->cold_part.p);
             if (g->n_ctl)   // (the listed tiles only: the short-tile walk gathers the rest itself)
                 hipLaunchKernelGGL(k_cold_trace, dim3(cdiv((int64_t)g->n_ctl * WAVE, 256)), dim3(256), 0, st,
                                    g->cold_off_p.p, g->cold_ops_p.p, g->sub[it & 1].p, g->ctl.p, g->n_ctl, g->T,
                                    g->cold_acc.p);
             MR_DEBUG_CHECK(ctx, "k_cold");
         }
-        if (any_wide && sst != st) MR_TRY_HIP(ctx, hipEventRecord(ctx->side_ev[1], sst));
-        if (blocks_fa) {
-            hipLaunchKernelGGL(tr_a, dim3(blocks_fa), dim3(plan.NT), lds_f, st, dv.p, ng, split_fa, d, alpha, it, 0);
+        if (side) MR_TRY_HIP(ctx, hipEventRecord(ctx->side_ev[1], sst));
+        if (L.blocks_fa) {
+            hipLaunchKernelGGL(L.tr_a, dim3(L.blocks_fa), dim3(plan.NT), L.lds_f, st, dv, ng, L.split_fa, d, alpha, it, 0);
             MR_DEBUG_CHECK(ctx, "k_tr_a");
-            if (any_wide && sst != st) MR_TRY_HIP(ctx, hipStreamWaitEvent(st, ctx->side_ev[1], 0));   // k_cold_ops done
+            if (side) MR_TRY_HIP(ctx, hipStreamWaitEvent(st, ctx->side_ev[1], 0));   // k_cold_ops done
             auto fx_b = [&](int mode, const MrPeerX& p) {
-                if (fb_small)
-                    hipLaunchKernelGGL(k_fx_b<FB_W_SMALL>, dim3(blocks_fb), dim3(WAVE * FB_W_SMALL), 0, st, dv.p, ng,
-                                       split_fb, d, it, mode, p);
-                else
-                    hipLaunchKernelGGL(k_fx_b<FB_W>, dim3(blocks_fb), dim3(WAVE * FB_W), 0, st, dv.p, ng, split_fb, d,
-                                       it, mode, p);
+                hipLaunchKernelGGL(fx_b_k, dim3(L.blocks_fb), dim3(fb_threads), 0, st, dv, ng, L.split_fb, d, it, mode, p);
             };
-            if (!coll) {
+            if (!L.coll) {
                 // (none: every graph finished by its last k_tr_a block; pf launches: the next k_tr_a
                 // finishes this iteration, k_fx_b only after the last one)
-                if (blocks_fb && (!launch_pf || it == iters - 1)) fx_b(0, px_off);
-            } else if (px_on) {   // the exchange fused into k_fx_b: push in mode 1, per-block waits in mode 2
-                fx_b(1, px);
-                if (!px.spin) MR_TRY(mr_peer_fx_wait(ctx, px, blocks_fb));
-                fx_b(2, px);
-                mr_peer_fx_round_done(ctx, &px);
+                if (L.blocks_fb && (!L.launch_pf || it == iters - 1)) fx_b(0, L.px_off);
+            } else if (L.px_on) {   // the exchange fused into k_fx_b: push in mode 1, per-block waits in mode 2
+                fx_b(1, L.px);
+                if (!L.px.spin) MR_TRY(mr_peer_fx_wait(ctx, L.px, L.blocks_fb));
+                fx_b(2, L.px);
+                mr_peer_fx_round_done(ctx, &L.px);
             } else {   // ONE all-reduce: the P_sr r limbs and every rank's r' max (exact: integers)
-                fx_b(1, px_off);
+                fx_b(1, L.px_off);
                 const int64_t nw = 2 * (int64_t)gs[0]->N + ctx->nranks;
                 const int prc = mr_peer_allreduce_u64(ctx, (unsigned long long*)gs[0]->fx_limb.p, nw);
                 if (prc == MR_ERR_STATE) MR_TRY(mr_coll_allreduce(ctx, gs[0]->fx_limb.p, nw, MR_DT_U64, 0));
                 else MR_TRY(prc);
-                fx_b(2, px_off);
+                fx_b(2, L.px_off);
             }
             MR_DEBUG_CHECK(ctx, "k_fx_b");
         }
-        if (blocks_a) {
-            if (fp32) hipLaunchKernelGGL(k_iter_a<float>, dim3(blocks_a), dim3(TB), lds, st, dv.p, ng, d, it);
-            else hipLaunchKernelGGL(k_iter_a<double>, dim3(blocks_a), dim3(TB), lds, st, dv.p, ng, d, it);
+        if (L.blocks_a) {
+            hipLaunchKernelGGL(iter_a, dim3(L.blocks_a), dim3(TB), L.lds, st, dv, ng, d, it);
             MR_DEBUG_CHECK(ctx, "k_iter_a");
         }
-        if (blocks_b) {
-            if (!coll) {
-                hipLaunchKernelGGL(k_iter_b, dim3(blocks_b), dim3(TB), 0, st, dv.p, ng, d, alpha, it, 0);
+        if (L.blocks_b) {
+            if (!L.coll) {
+                hipLaunchKernelGGL(k_iter_b, dim3(L.blocks_b), dim3(TB), 0, st, dv, ng, d, alpha, it, 0);
             } else {   // ONE all-reduce: the per-op P_sr r sums (fp64 SUM) and every rank's r' max
-                hipLaunchKernelGGL(k_iter_b, dim3(blocks_b), dim3(TB), 0, st, dv.p, ng, d, alpha, it, 1);
+                hipLaunchKernelGGL(k_iter_b, dim3(L.blocks_b), dim3(TB), 0, st, dv, ng, d, alpha, it, 1);
                 const int64_t nw = (int64_t)gs[0]->N + ctx->nranks;
                 const int prc = mr_peer_allreduce_f64(ctx, gs[0]->op_sum.p, nw);
                 if (prc == MR_ERR_STATE) MR_TRY(mr_coll_allreduce(ctx, gs[0]->op_sum.p, nw, MR_DT_F64, 0));
                 else MR_TRY(prc);
-                hipLaunchKernelGGL(k_iter_b, dim3(blocks_b), dim3(TB), 0, st, dv.p, ng, d, alpha, it, 2);
+                hipLaunchKernelGGL(k_iter_b, dim3(L.blocks_b), dim3(TB), 0, st, dv, ng, d, alpha, it, 2);
             }
             MR_DEBUG_CHECK(ctx, "k_iter_b");
         }
-        mr_prof_end(ctx, bytes);
+        mr_prof_end(ctx, L.bytes);
     }
+    return MR_OK;
+}
+
+// The error words of ng graphs (4 per graph: kind-hash collision, division by zero, partition
+// overflow), graph by graph: a collision makes the caller retry with the next seed
+static int decode_error_words(mr_ctx* ctx, const int32_t* words, const int* anomaly, int ng, bool* collided) {
+    *collided = false;
+    for (int i = 0; i < ng; ++i) {
+        const int32_t* w = words + 4 * (size_t)i;
+        *collided = w[0] & 1;
+        if (*collided) return MR_OK;
+        if (w[2] & 1) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: a partition exceeded its table");
+        if (anomaly[i] && (w[1] & 1)) return mr_fail(ctx, MR_ERR_ZERODIV, "float division by zero");
+    }
+    return MR_OK;
+}
+
+// One attempt with kind-hash seed `seed`; *collided reports a 64-bit key collision found by the
+// exact verification (k_kind_verify / k_sh_kind_check), after which the caller retries.
+// as: enqueue only (window groups); mr_pagerank_async_finish reads the error words
+static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
+                            int iters, int precision, uint32_t flags, bool sharded, uint64_t seed, uint64_t hmask,
+                            bool* collided, PrAsync* as = nullptr) {
+    *collided = false;
+    HostMarks hm(ng);
+    MR_TRY(attempt_check(ctx, gs, anomaly, ng, iters, sharded));
+    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool fp32 = precision == MR_FP32;
+    PrAsync own;   // what the kernels read lives until the final sync of a call that waits, else in the caller's `as`
+    PrAsync& s = as ? *as : own;
+    MR_TRY(attempt_setup(ctx, gs, anomaly, ng, d, fp32, flags, sharded, seed, hmask, s.setup_h, s.setup_d));
+    hm.mark("setup");
+    const FxPlan plan = fx_plan(gs, ng, fp32, sharded);
+    std::vector<int64_t> nfa;
+    MR_TRY(cut_blocks(ctx, gs, ng, plan, hm, nfa));   // (marks "blocks" before its launches)
+    uint64_t cold_span_all = 1;
+    MR_TRY(cold_span_over_ranks(ctx, gs, ng, sharded, &cold_span_all));
+    // ---- batched power iteration: one k_tr_a (+ k_fx_b) or k_iter_a + k_iter_b per iteration for every graph
+    s.hv = std::vector<GDev>((size_t)ng);   // (value-initialised: the kernels read the fields a path leaves out as 0)
+    const TrKnobs kn;
+    Launch L;
+    int64_t fb16 = 0;   // k_fx_b blocks of the launch at 16 ops per block
+    for (int i = 0; i < ng; ++i)
+        if (gs[i]->fused) fb16 += cdiv(gs[i]->N, 16);
+    for (int i = 0; i < ng; ++i) {
+        GDev& v = s.hv[(size_t)i];
+        gdev_pointers(v, ctx, gs[i], fp32, alpha, plan);
+        gdev_scales(v, gs[i], sharded, cold_span_all);
+        gdev_launch(v, gs[i], nfa[(size_t)i], fp32, sharded, plan, kn, fb16 > FB_MANY_BLOCKS, L);
+    }
+    MR_TRY(finalise_launch(ctx, gs, ng, fp32, sharded, plan, kn, s.hv, L));
+    hm.mark("descr");
+    MR_TRY(s.dv.upload(ctx, s.hv.data(), s.hv.size()));
+    MR_TRY(prepare_exchange(ctx, gs, ng, L));
+    hm.mark("pre-loop");
+    MR_TRY(iterate(ctx, gs, ng, fp32, d, alpha, iters, plan, s.hv, s.dv.p, L));
     // weights of every graph and the gathered error words in one launch (the flags are final:
     // the kernels that raise them ran before the iterations; a sharded graph's words meet in a
     // MAX first, below, so it reads them after that)
-    DBuf<int32_t> fl;
+    DBuf<int32_t>& fl = s.fl;
     MR_TRY(fl.alloc(ctx, (size_t)4 * ng));
     hm.mark("loop");
-    hipLaunchKernelGGL(k_weights_batch, dim3(ng), dim3(1024), 0, st, dv.p, iters, (int)((flags & MR_PR_EXACT_SUMS) != 0),
-                       fl.p);
+    hipLaunchKernelGGL(k_weights_batch, dim3(ng), dim3(1024), 0, st, s.dv.p, iters,
+                       (int)((flags & MR_PR_EXACT_SUMS) != 0), fl.p);
     MR_DEBUG_CHECK(ctx, "k_weights_batch");
     MR_TRY_HIP(ctx, hipGetLastError());
-    if (coll && ctx->peer_on) MR_TRY(mr_peer_check(ctx, "peer all-reduce"));   // an error, not wrong sums
+    if (L.coll && ctx->peer_on) MR_TRY(mr_peer_check(ctx, "peer all-reduce"));   // an error, not wrong sums
     // a shard's local collision must make every rank retry: the error words meet in a MAX
-    if (coll) {
+    if (L.coll) {
         MR_TRY(mr_coll_allreduce(ctx, gs[0]->flag.p, 4, MR_DT_I32, 1));
         MR_TRY_HIP(ctx, hipMemcpyAsync(fl.p, gs[0]->flag.p, 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }
     if (as) {   // enqueued only: the words go to the caller's pinned slot, the finish reads them
-        as->setup_h = std::move(setup_h);
-        as->setup_d.swap(setup_d);
-        as->hv = std::move(hv);
-        as->dv.swap(dv);
-        as->fl.swap(fl);
         as->anomaly.assign(anomaly, anomaly + ng);
         as->ng = ng;
         return as->defer ? MR_OK : mr_pagerank_async_commit(ctx, as);
@@ -4927,15 +5001,7 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
         MR_TRY(fl.download(ctx, hflag.data(), hflag.size()));
         MR_TRY_HIP(ctx, hipStreamSynchronize(st));
     }
-    for (int i = 0; i < ng; ++i) {
-        if (hflag[(size_t)4 * i] & 1) {
-            *collided = true;
-            return MR_OK;
-        }
-        if (hflag[(size_t)4 * i + 2] & 1) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: a partition exceeded its table");
-        if (anomaly[i] && (hflag[(size_t)4 * i + 1] & 1)) return mr_fail(ctx, MR_ERR_ZERODIV, "float division by zero");
-    }
-    return MR_OK;
+    return decode_error_words(ctx, hflag.data(), anomaly, ng, collided);
 }
 
 // A 64-bit set-hash collision between two different trace kinds is caught by the exact
@@ -5306,16 +5372,7 @@ int mr_pagerank_async_finish(mr_ctx* ctx, PrAsync* a, bool* rerun) {
     *rerun = false;
     if (!a->committed) MR_TRY(mr_pagerank_async_commit(ctx, a));   // (a deferred batch nobody committed)
     MR_TRY_HIP(ctx, hipEventSynchronize(a->ev));
-    for (int i = 0; i < a->ng; ++i) {
-        const int32_t* w = a->hflag + 4 * i;
-        if (w[0] & 1) {   // a kind-hash collision: the caller reruns
-            *rerun = true;
-            return MR_OK;
-        }
-        if (w[2] & 1) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: a partition exceeded its table");
-        if (a->anomaly[(size_t)i] && (w[1] & 1)) return mr_fail(ctx, MR_ERR_ZERODIV, "float division by zero");
-    }
-    return MR_OK;
+    return decode_error_words(ctx, a->hflag, a->anomaly.data(), a->ng, rerun);   // (a collision: the caller reruns)
 }
 void mr_pagerank_async_free(PrAsync* a) { delete a; }
 
