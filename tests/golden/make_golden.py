@@ -282,6 +282,36 @@ def stream_case(name, params, outdir):
           res["driver_stdout"].count("anomaly_list"), "time %.1fs" % res["timing_s"])
 
 
+DICT_GENERAL = dict(N=300, T=1500, seed=3)
+
+
+def dict_general(outdir):
+    """trace_pagerank on dicts get_pagerank_graph never produces (tests/gpu_util.general_graph:
+    P_rs != P_sr, a pr_trace subset with its own lengths, traces without ops, list multiplicities) at
+    a size past one block and one tile.  The dicts are stored in index form (not re-derived from
+    the seed: another numpy's Generator stream must not change the fixture) with both outputs."""
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from gpu_util import general_graph, graph_dicts
+
+    oo, ot, to, pt = graph_dicts(general_graph(**DICT_GENERAL))
+    nodes, traces = list(oo.keys()), list(ot.keys())
+    ni = {n: i for i, n in enumerate(nodes)}
+    ti = {n: i for i, n in enumerate(traces)}
+    flat = lambda d, kmap, vmap: {"keys": [kmap[k] for k in d], "len": [len(v) for v in d.values()],
+                                  "vals": [vmap[x] for v in d.values() for x in v]}
+    res = {"name": "dict_general", "params": DICT_GENERAL, "nodes": nodes, "traces": traces,
+           "operation_operation": flat(oo, ni, ni), "operation_trace": flat(ot, ti, ni),
+           "trace_operation": flat(to, ni, ti), "pr_trace": flat(pt, ti, ni)}
+    for anomaly in (False, True):
+        t0 = time.perf_counter()
+        w, c = ref_pr.trace_pagerank(oo, ot, to, pt, anomaly)
+        print("dict_general anomaly", anomaly, "pr time %.1fs" % (time.perf_counter() - t0))
+        res[f"anomaly={anomaly}"] = dump_pr(w, c)
+    with open(os.path.join(outdir, "dict_general.json"), "w") as f:
+        json.dump(res, f, separators=(",", ":"))
+
+
 C3_WINDOW = dict(n_ops=500, n_traces=20_000, seed=4242, branch=1.9, p_max=0.8, fault_ms=6000.0)
 
 
@@ -348,6 +378,9 @@ def main():
     if sys.argv[1:] == ["span_times"]:
         span_times_case(outdir)
         return
+    if sys.argv[1:] == ["dict_general"]:
+        dict_general(outdir)
+        return
     man = {"numpy": np.__version__, "pandas": pd.__version__, "python": sys.version.split()[0]}
     try:
         cfg = np.show_config(mode="dicts")
@@ -381,6 +414,7 @@ def main():
                               "out": run_spectrum_all(a_w, n_w, 4, 5, a_n, n_n)}
     with open(os.path.join(outdir, "dict_cases.json"), "w") as f:
         json.dump(dres, f, indent=0)
+    dict_general(outdir)
     # span-level: hand-built edges
     edf = edge_span_df()
     e = {}

@@ -44,6 +44,61 @@ def test_dict_cases(case, anomaly):
     check_pr(orc.trace_pagerank(*args, anomaly), exp)
 
 
+@pytest.mark.parametrize("anomaly", [False, True])
+def test_dict_general(anomaly):
+    """The general dict form at 300 ops / 1500 traces (gpu_util.general_graph: P_rs != P_sr, a
+    pr_trace subset with its own lengths, traces without ops, list multiplicities) against the
+    reference's own output on the recorded dicts.  1e-10: the reference's dense dgemv sums 1500
+    terms in another order (measured 5e-15); keys, counts and zeros exact."""
+    from gpu_util import general_golden_dicts
+
+    fix = load_golden("dict_general.json")
+    exp = fix[f"anomaly={anomaly}"]
+    got = orc.trace_pagerank(*general_golden_dicts(fix), anomaly)
+    check_pr(got, exp, rtol=1e-10)
+    gw, ew = np.array([float(v) for v in got[0].values()]), unhex(exp["weight"])
+    np.testing.assert_array_equal(gw == 0, ew == 0)
+
+
+def test_dict_general_fixture_is_a_general_graph():
+    """The recorded dicts (stored, not re-derived from the seed) have the properties the fixture is
+    there for, and graph_dicts inverts graph_from_dicts on them."""
+    from gpu_util import general_golden_dicts, graph_dicts
+
+    dicts = general_golden_dicts(load_golden("dict_general.json"))
+    g = orc.graph_from_dicts(*dicts)
+    assert (g.N, g.T) == (300, 1500)
+    assert not (np.array_equal(g.rs_t, g.sr_t) and np.array_equal(g.rs_o, g.sr_o))
+    assert g.pr_idx.size < g.T and (np.diff(g.pr_idx) < 0).any()
+    assert (g.len_t == 0).any() and (g.len_t > np.bincount(g.sr_t, minlength=g.T)).any()
+    assert (g.len_o > np.bincount(g.rs_o, minlength=g.N)).any() and (g.nchild > np.bincount(g.ss_p, minlength=g.N)).any()
+    again = graph_dicts(g)
+    assert all(a == b and list(a) == list(b) for a, b in zip(again, dicts))
+
+
+def test_host_graph_from_dicts_equals_oracle_conversion():
+    """The product's dict -> index conversion (graph.host_graph_from_dicts) against the oracle's
+    (graph_from_dicts -> host_graph_from_oracle), field for field, on the general dicts (explicit
+    rs_* and pr_*) and on their rs == sr / pr_trace-is-operation_trace form (both None)."""
+    from gpu_util import general_golden_dicts, general_graph, graph_dicts, host_graph_from_oracle
+    from microrank_amd.graph import host_graph_from_dicts
+
+    general = general_golden_dicts(load_golden("dict_general.json"))
+    plain = graph_dicts(general_graph(300, 200, seed=5, rs_drop=0, rs_add=0, pr_frac=None, empty_frac=0))
+    for dicts, explicit in ((general, True), (plain, False)):
+        got = host_graph_from_dicts(*dicts)
+        exp = host_graph_from_oracle(orc.graph_from_dicts(*dicts))
+        assert got.nodes == exp.nodes and got.traces == exp.traces
+        for f in ("sr_off", "sr_ops", "rs_off", "rs_ops", "len_t", "len_o", "ss_off", "ss_par", "nchild", "pr_trace",
+                  "pr_len"):
+            a, b = getattr(got, f), getattr(exp, f)
+            if f.startswith(("rs_", "pr_")):
+                assert (a is not None) == (b is not None) == explicit, f
+            if b is not None:
+                assert a.dtype == b.dtype, f
+                np.testing.assert_array_equal(a, b, err_msg=f)
+
+
 def test_paper_example_survey_values():
     # SURVEY §4: anomaly weights of the Fig. 3 dicts through the reference
     d = load_golden("dict_cases.json")["fig3"]
