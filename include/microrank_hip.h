@@ -121,6 +121,34 @@ int mr_pagerank_ex(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha
  * ranked together: one launch per Jacobi iteration covers every graph */
 int mr_pagerank_batch(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, int n_graphs, double d,
                       double alpha, int iters, int precision, uint32_t flags);
+/* mr_pagerank_batch with a convergence report and an optional early stop.  The reference iterates
+ * a fixed 25 times (pagerank.py:117) and its README's production notices say a large system
+ * "needs more iterations in PageRank" (README.md:37); nothing there says whether a count was
+ * enough.  After every iteration k = 1, 2, ... the device records, per graph,
+ *   resid[k-1] = max over ops of | s_k - s_{k-1} |,
+ * s_k the max-normalised vector the reference holds in `s` after k iterations (pagerank.py:126;
+ * s_0 = 1/(N+T), :118).  Every check_every iterations, and at max_iters, the host reads the
+ * history and stops at the first such check K where every graph's resid[K-1] <= tol.  tol == 0:
+ * no intermediate reads, the call runs max_iters iterations and reads the history once.
+ * phi as mr_pagerank_ex's.  fp32 residuals bottom out near 6e-8 (one fp32 ulp of a vector whose
+ * maximum is 1): a smaller tol with MR_FP32 runs to max_iters.
+ * Contract: after a call that ran K = *iters_done iterations, every graph's weights and coverage
+ * (mr_graph_fetch) are bitwise those of mr_pagerank_batch(..., iters = K, ...) on the same graphs.
+ * MR_ERR_ARG: null pointers (converged_at may be NULL), n_graphs < 1, max_iters < 1,
+ * check_every < 1, tol negative or NaN, phi <= 0 -- and the three forms this entry does not cover:
+ * MR_PR_KIND_COMPRESS, a graph built by mr_graph_build_sharded (an early stop must be agreed over
+ * the ranks; mr_pagerank_sharded takes a count), and window batches (mr_windows_batch and
+ * mr_rca_window rank with their fixed count and have no convergence form).  Everything else as
+ * mr_pagerank_batch: its errors, the kind-hash collision retry (which reruns the attempt and
+ * overwrites the history), mr_graph_fetch afterwards. */
+int mr_pagerank_converge(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, int n_graphs,
+                         double d, double alpha, int max_iters, double phi, int precision, uint32_t flags,
+                         double tol, int check_every,
+                         int32_t* iters_done,              /* out: iterations every graph ran */
+                         double* resid,                    /* [n_graphs * max_iters] host; graph g's history at
+                                                              g * max_iters; entries >= iters_done are 0.0 */
+                         int32_t* converged_at);           /* [n_graphs] host: first k (1-based) with
+                                                              resid[k-1] <= tol, -1 if none; may be NULL */
 int mr_graph_fetch(mr_graph* g, double* weight /*[N] host*/, int32_t* coverage /*[N] host*/,
                    double* kind /*[T] host or NULL*/, float* pref /*[T] host or NULL*/);
 

@@ -2756,6 +2756,7 @@ extern "C" int mr_graph_build_sharded(mr_ctx* ctx, const mr_spans* sp, const uin
     MR_TRY(mask.upload(ctx, trace_mask, (size_t)sp->n_traces));
     auto g = new mr_graph();
     g->ctx = ctx;
+    g->shard_built = true;
     int rc = graph_build_indexed(ctx, sp, mask.p, g, true);
     if (rc == MR_OK) {
         g->rs_is_sr = true;

@@ -279,6 +279,7 @@ struct mr_graph {
     bool force_tile = false;       // the ranks of a sharded graph agreed on the tile path
     int64_t T_all = 0;             // traces over all shards (0: this graph is whole)
     bool sharded_done = false;     // mr_pagerank_sharded's graph-level exchange has run
+    bool shard_built = false;      // built by mr_graph_build_sharded (mr_pagerank_converge rejects it)
     DBuf<uint64_t> fx_part;   // [n_blocks * N]
     DBuf<double> fx_ssv;      // [N] alpha * (P_ss s_k)[o] / M_s(k), from k_fx_a for k_fx_b
     DBuf<uint64_t> fx_limb;   // [2N] sharded graphs: exact limb sums per op, all-reduced per iteration

@@ -1,0 +1,95 @@
+// What the power iteration's kernels share across translation units (mr_pagerank.hip's iteration,
+// mr_converge.hip's residual): the maxima ring and a graph's device descriptor.
+#pragma once
+#include "mr_internal.h"
+
+// M_s / M_r per iteration live in MSH shards (an atomicMax per block or op on ONE word would
+// serialise ~2k same-address atomics per iteration); readers reduce the shards.
+constexpr int MSH = 64;
+// mslot: [3 iterations][s | r][MSH] maxima, then words of the hand-offs (6 MSH + 1: the last-block ticket)
+constexpr int MSLOT_WORDS = 6 * MSH + 8;
+__device__ __forceinline__ double bits2d(unsigned long long b) { return __longlong_as_double((long long)b); }
+__device__ __forceinline__ unsigned long long d2bits(double v) {
+    return (unsigned long long)__double_as_longlong(v);
+}
+
+// Per-graph view for the batched iteration: one k_iter_a / k_iter_b pair per Jacobi iteration
+// covers every graph of a batch (the two graphs of an RCA window, or many windows); graph i owns
+// blocks [blk0, blk0 + n_tb + n_tiles) of k_iter_a and [blk0b, blk0b + n_ob) of k_iter_b.
+struct GDev {
+    const int64_t* rs_off;
+    const int32_t* rs_ops;
+    const uint16_t* rs16;       // u16 copy of rs_ops (N <= 65536) or null
+    const uint16_t* rsw;        // the fused kernel's ids: rs16, or rsp in relabelled ops
+    const int32_t* perm;        // relabelled ops: perm[new] = old (null: identity)
+    int32_t n_hot;              // k_tr_a: su of ops [0, n_hot) in LDS (relabelled graphs)
+    const uint16_t* tids;       // k_tr_a: lane-interleaved id chunks of the wave tiles
+    const int32_t* coff;        // [n_wt+1] first chunk of a tile
+    const int32_t* wtile;       // [waves+1] first tile of each wave of the launch
+    const float* c_tp;          // c_t, w_t in position order (tperm)
+    const float* w_tp;
+    const double* mw_tp;        // kind-compressed graphs: w_t * multiplicity (position order), else null
+    const uint8_t* hmask;       // register-accumulated hot ops: trace bits in position order (nhr > 0)
+    const uint8_t* trun;        // layout-order graphs: run lengths of identical traces by position (or null)
+    const uint32_t* ctids;      // wide graphs: cold chunks of the short-tile walk ([chunk][lane] x 2 labels)
+    const int32_t* ccoff;       // [n_wt+1] first cold chunk of a tile
+    int32_t nhr;
+    int32_t hop[8];
+    const float* c_t;
+    const float* w_t;
+    const float* u_o;
+    const float* pw;
+    const uint16_t* ltr;
+    const int64_t* pr_beg;
+    const int32_t* tile_pr0;
+    const int32_t* lp;
+    const int32_t* tile_lp0;
+    const int32_t* op_pr_off;
+    const int32_t* op_pr;
+    const int64_t* ss_off;
+    const int32_t* ss_par;
+    void* q[2];
+    double* sub[2];
+    float* suf[2];                 // su32 graphs: the same su as floats (k_tr_a EXT & 8 gathers these)
+    double* spb[2];
+    double* part;
+    unsigned long long* mslot;
+    double *sn, *weight, *scal;    // k_weights_batch: normalised s, weights, scalars
+    const int32_t* flag;           // the graph's error words (gathered after the iterations)
+    unsigned long long* fx_part;
+    double* fx_ssv;
+    unsigned long long* fx_limb;   // sharded: [2N] (lo, hi) limb sums per op, then [nranks] r' maxima
+    int32_t rank, nranks;          // sharded: this rank's slot of the r' maxima appended to the sum
+    double* op_sum;                // sharded tile path: [N] pair-partial sums per op
+    double fx_scale, fx_iscale;
+    const double* dscale;          // k_tr_a graphs cut on the device: {2^SC, 2^-SC} (k_tr_cut), else null
+    // wide fused graphs: k_tr_a's ops [0, NA) (NA = N otherwise); ops [NA, N) in ranges of
+    // cold_rw ops whose rows (cold_part, blocks cold_rowbase[r] .. [r+1]) carry scale cx_scale
+    int32_t NA, cold_rw;
+    int32_t ns_warm;               // k_tr_a EXT & 8: labels [NA, ns_warm) have their su in LDS (else NA)
+    int32_t su32;                  // fp32 wide graphs: su rounded to float where k_fx_b makes it
+    const double* cold_acc;        // [T] per position: the cold half of the trace's su sum
+    const unsigned long long* cold_part;
+    const int32_t* cold_rowbase;
+    double cx_scale, cx_iscale;
+    double alpha;                  // P_ss weight (k_fx_b's call-graph term)
+    int32_t T, N, n_tb, n_tiles, tshift, lds_su, blk0, n_ob, blk0b;
+    int32_t blk0f, n_fa, blk0fb, n_fb;   // fused path: k_tr_a / k_fx_b block ranges
+    int32_t fb_ops;                      // k_fx_b ops per block
+    int32_t lastfin;                     // k_tr_a's last block of the graph finishes the iteration (no k_fx_b)
+    int32_t pf;                          // k_tr_a(it) first finishes iteration it - 1 itself (no k_fx_b between)
+    int64_t pf_stride;                   // pf: words of one partial-row buffer (rows and terms double-buffered)
+    int32_t lf_acq;                      // lastfin: the finishing block takes an agent acquire (else the launch
+                                         // runs one workgroup per CU and the sc1 hand-off of the guide's row 1 holds)
+    int32_t ssv_pre;                     // k_tr_a's blocks compute the call-graph terms (fx_ssv) for k_fx_b
+    int32_t row_wt;                      // k_tr_a's partial rows stored write-through (sc1)
+    int32_t blk0r;                       // k_resid: the graph's first block (RESID_OPS ops per block)
+};
+
+// The convergence residual (mr_converge.hip): after iteration `it` of a launch's ng graphs,
+// resid[g * max_iters + it] = bits of max_o |spb[(it+1)&1][o] / M_s(it+1) - spb[it&1][o] / M_s(it)|,
+// one block per RESID_OPS ops of a graph (GDev::blk0r; `blocks` over the launch).  The words are
+// zero before the loop (an integer max of non-negative doubles' bits: order-free).
+constexpr int32_t RESID_OPS = 4096;
+void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int max_iters,
+                     unsigned long long* resid);

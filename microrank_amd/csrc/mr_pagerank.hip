@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "mr_internal.h"
+#include "mr_iter_dev.h"
 #include "mr_prim.h"
 #include "mr_sort.h"
 
@@ -1408,16 +1409,7 @@ __global__ void k_inv_perm(const int32_t* __restrict__ perm, int32_t n, int32_t*
 }
 
 // ---------------------------------------------------------------- iteration
-// M_s / M_r per iteration live in MSH shards (an atomicMax per block or op on ONE word would
-// serialise ~2k same-address atomics per iteration); readers reduce the shards.
-constexpr int MSH = 64;
-// mslot: [3 iterations][s | r][MSH] maxima, then words of the hand-offs (6 MSH + 1: the last-block ticket)
-constexpr int MSLOT_WORDS = 6 * MSH + 8;
-__device__ __forceinline__ double bits2d(unsigned long long b) { return __longlong_as_double((long long)b); }
-__device__ __forceinline__ unsigned long long d2bits(double v) {
-    return (unsigned long long)__double_as_longlong(v);
-}
-
+// (the maxima ring -- MSH, MSLOT_WORDS, bits2d / d2bits -- and GDev: mr_iter_dev.h)
 constexpr int TR_PAD = WAVE;   // k_tr_a's pad ids N .. N + 63 (su = 0)
 __device__ __forceinline__ int32_t cdiv_d(int32_t a, int32_t b) { return (a + b - 1) / b; }
 // The iteration state (thread i: word i of each buffer); v0 = 1 / (N + traces of the whole graph,
@@ -1659,78 +1651,6 @@ __global__ void k_lo_apply_b(const LDev* __restrict__ ld, int32_t n) {
     if (i < 4) G.flag[i] = 0;
     if (i < 8 && i != 2 && i != 3) G.scal[i] = 0.0;
 }
-
-// Per-graph view for the batched iteration: one k_iter_a / k_iter_b pair per Jacobi iteration
-// covers every graph of a batch (the two graphs of an RCA window, or many windows); graph i owns
-// blocks [blk0, blk0 + n_tb + n_tiles) of k_iter_a and [blk0b, blk0b + n_ob) of k_iter_b.
-struct GDev {
-    const int64_t* rs_off;
-    const int32_t* rs_ops;
-    const uint16_t* rs16;       // u16 copy of rs_ops (N <= 65536) or null
-    const uint16_t* rsw;        // the fused kernel's ids: rs16, or rsp in relabelled ops
-    const int32_t* perm;        // relabelled ops: perm[new] = old (null: identity)
-    int32_t n_hot;              // k_tr_a: su of ops [0, n_hot) in LDS (relabelled graphs)
-    const uint16_t* tids;       // k_tr_a: lane-interleaved id chunks of the wave tiles
-    const int32_t* coff;        // [n_wt+1] first chunk of a tile
-    const int32_t* wtile;       // [waves+1] first tile of each wave of the launch
-    const float* c_tp;          // c_t, w_t in position order (tperm)
-    const float* w_tp;
-    const double* mw_tp;        // kind-compressed graphs: w_t * multiplicity (position order), else null
-    const uint8_t* hmask;       // register-accumulated hot ops: trace bits in position order (nhr > 0)
-    const uint8_t* trun;        // layout-order graphs: run lengths of identical traces by position (or null)
-    const uint32_t* ctids;      // wide graphs: cold chunks of the short-tile walk ([chunk][lane] x 2 labels)
-    const int32_t* ccoff;       // [n_wt+1] first cold chunk of a tile
-    int32_t nhr;
-    int32_t hop[8];
-    const float* c_t;
-    const float* w_t;
-    const float* u_o;
-    const float* pw;
-    const uint16_t* ltr;
-    const int64_t* pr_beg;
-    const int32_t* tile_pr0;
-    const int32_t* lp;
-    const int32_t* tile_lp0;
-    const int32_t* op_pr_off;
-    const int32_t* op_pr;
-    const int64_t* ss_off;
-    const int32_t* ss_par;
-    void* q[2];
-    double* sub[2];
-    float* suf[2];                 // su32 graphs: the same su as floats (k_tr_a EXT & 8 gathers these)
-    double* spb[2];
-    double* part;
-    unsigned long long* mslot;
-    double *sn, *weight, *scal;    // k_weights_batch: normalised s, weights, scalars
-    const int32_t* flag;           // the graph's error words (gathered after the iterations)
-    unsigned long long* fx_part;
-    double* fx_ssv;
-    unsigned long long* fx_limb;   // sharded: [2N] (lo, hi) limb sums per op, then [nranks] r' maxima
-    int32_t rank, nranks;          // sharded: this rank's slot of the r' maxima appended to the sum
-    double* op_sum;                // sharded tile path: [N] pair-partial sums per op
-    double fx_scale, fx_iscale;
-    const double* dscale;          // k_tr_a graphs cut on the device: {2^SC, 2^-SC} (k_tr_cut), else null
-    // wide fused graphs: k_tr_a's ops [0, NA) (NA = N otherwise); ops [NA, N) in ranges of
-    // cold_rw ops whose rows (cold_part, blocks cold_rowbase[r] .. [r+1]) carry scale cx_scale
-    int32_t NA, cold_rw;
-    int32_t ns_warm;               // k_tr_a EXT & 8: labels [NA, ns_warm) have their su in LDS (else NA)
-    int32_t su32;                  // fp32 wide graphs: su rounded to float where k_fx_b makes it
-    const double* cold_acc;        // [T] per position: the cold half of the trace's su sum
-    const unsigned long long* cold_part;
-    const int32_t* cold_rowbase;
-    double cx_scale, cx_iscale;
-    double alpha;                  // P_ss weight (k_fx_b's call-graph term)
-    int32_t T, N, n_tb, n_tiles, tshift, lds_su, blk0, n_ob, blk0b;
-    int32_t blk0f, n_fa, blk0fb, n_fb;   // fused path: k_tr_a / k_fx_b block ranges
-    int32_t fb_ops;                      // k_fx_b ops per block
-    int32_t lastfin;                     // k_tr_a's last block of the graph finishes the iteration (no k_fx_b)
-    int32_t pf;                          // k_tr_a(it) first finishes iteration it - 1 itself (no k_fx_b between)
-    int64_t pf_stride;                   // pf: words of one partial-row buffer (rows and terms double-buffered)
-    int32_t lf_acq;                      // lastfin: the finishing block takes an agent acquire (else the launch
-                                         // runs one workgroup per CU and the sc1 hand-off of the guide's row 1 holds)
-    int32_t ssv_pre;                     // k_tr_a's blocks compute the call-graph terms (fx_ssv) for k_fx_b
-    int32_t row_wt;                      // k_tr_a's partial rows stored write-through (sc1)
-};
 
 // graph owning block `blk` of launch kind `which` (0 k_iter_a, 1 k_iter_b, 2 k_tr_a, 3 k_fx_b);
 // the start offsets are non-decreasing over graphs (graphs without blocks in a launch repeat it)
@@ -3362,7 +3282,8 @@ struct FxPlan {
     bool pf = false;    // window batches: the next launch finishes an iteration (k_tr_a's pf prologue)
     bool w32 = false;   // fp32 wide graphs only: float su and warm labels in LDS (k_tr_a EXT & 8)
 };
-static FxPlan fx_plan(mr_graph* const* gs, int ng, bool fp32, bool sharded) {
+// allow_pf false: k_fx_b every iteration, as under MR_TR_PF=0 (a call that reads the ring between launches)
+static FxPlan fx_plan(mr_graph* const* gs, int ng, bool fp32, bool sharded, bool allow_pf = true) {
     FxPlan P;
     int32_t nmax = 0;
     int64_t tmax = 0;
@@ -3388,7 +3309,7 @@ static FxPlan fx_plan(mr_graph* const* gs, int ng, bool fp32, bool sharded) {
     // launches -- every graph fused and plain (no multiplicities, cold sums, merged runs, hot
     // ops or relabelling), N <= PF_NMAX (three N-word LDS arrays, four blocks per CU).
     // MR_TR_PF=0 (read per call; A/B and tests): k_fx_b every iteration
-    P.pf = knob_on("MR_TR_PF") && !sharded && ng >= 2 && P.NT == 512 && P.mode == WV_SU_ALL;
+    P.pf = allow_pf && knob_on("MR_TR_PF") && !sharded && ng >= 2 && P.NT == 512 && P.mode == WV_SU_ALL;
     for (int i = 0; i < ng && P.pf; ++i) {
         const mr_graph* g = gs[i];
         P.pf = g->fused && !g->wide && !g->relabeled && !g->nhr && !g->mw_tp.p && kern_n(g) <= PF_NMAX &&
@@ -4612,6 +4533,7 @@ struct TrKnobs {
 // (gdev_launch), then the launch's variant and streams (finalise_launch, prepare_exchange)
 struct Launch {
     int32_t blocks_a = 0, blocks_b = 0, blocks_fa = 0, blocks_fb = 0;   // k_iter_a / k_iter_b / k_tr_a / k_fx_b
+    int32_t blocks_r = 0;                   // k_resid (launched only for a convergence request)
     size_t lds = VCAP * sizeof(double), lds_f = 0;   // k_iter_a's / k_tr_a's LDS bytes
     double bytes = 0.0;                     // algorithmic bytes of one iteration (profiling)
     int32_t split_fa = 0, split_fb = 0;     // two graphs: the second one's first block (no search)
@@ -4621,6 +4543,17 @@ struct Launch {
     bool coll = false, any_wide = false, px_on = false;
     hipStream_t sst = nullptr;              // k_cold_ops' stream (the side stream, or the main one)
     MrPeerX px{}, px_off{};                 // the peer exchange inside k_fx_b (px_on), and none
+};
+
+// A convergence request (mr_pagerank_converge): the attempt records every iteration's residual
+// (k_resid), reads the history every check_every iterations and at max_iters, and stops at the first
+// such check K where every graph's resid[K - 1] <= tol.  tol == 0: no intermediate reads.
+struct Converge {
+    double tol;
+    int check_every, max_iters;
+    unsigned long long* resid_dev;   // [ng * max_iters] bits of the residuals, zeroed by the attempt
+    double* resid;                   // [ng * max_iters] host: the history, entries >= iters_done 0.0
+    int iters_done;                  // out: iterations every graph ran
 };
 
 // A graph's descriptor, part 1: its arrays and sizes, field for field
@@ -4742,6 +4675,8 @@ static void gdev_launch(GDev& v, const mr_graph* g, int64_t nfa, bool fp32, bool
     L.blocks_fb += v.n_fb;
     v.blk0 = L.blocks_a;
     v.blk0b = L.blocks_b;
+    v.blk0r = L.blocks_r;
+    L.blocks_r += cdiv(g->N, RESID_OPS);
     L.bytes += iter_bytes(g, fp32);
     if (g->fused) {   // no tile-path blocks (n_tb = n_tiles = n_ob = 0)
         L.lds_f = std::max(L.lds_f, plan_lds(kern_n(g), plan));
@@ -4840,15 +4775,18 @@ static int prepare_exchange(mr_ctx* ctx, mr_graph* const* gs, int ng, Launch& L)
 
 // The power iteration: per iteration the wide graphs' cold halves, k_tr_a + k_fx_b for the fused graphs
 // and k_iter_a + k_iter_b for the others, a sharded graph's all-reduce between each pair's halves
-static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d, double alpha, int iters,
-                   const FxPlan& plan, const std::vector<GDev>& hv, const GDev* dv, Launch& L) {
+// Iterations [it_begin, it_end) of the call; cv: the residual of each goes to its history (k_resid,
+// outside the roofline bracket)
+static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d, double alpha, int it_begin, int it_end,
+                   const FxPlan& plan, const std::vector<GDev>& hv, const GDev* dv, Launch& L,
+                   const Converge* cv = nullptr) {
     hipStream_t st = ctx->stream, sst = L.sst;
     const bool side = L.any_wide && sst != st;
     const auto cold_ops = fp32 ? k_cold_ops<float> : k_cold_ops<double>;
     const auto iter_a = fp32 ? k_iter_a<float> : k_iter_a<double>;
     const auto fx_b_k = L.fb_small ? k_fx_b<FB_W_SMALL> : k_fx_b<FB_W>;
     const int fb_threads = WAVE * (L.fb_small ? FB_W_SMALL : FB_W);
-    for (int it = 0; it < iters; ++it) {
+    for (int it = it_begin; it < it_end; ++it) {
         mr_prof_begin(ctx);
         if (side) {
             MR_TRY_HIP(ctx, hipEventRecord(ctx->side_ev[0], st));   // this iteration's su and q are ready
@@ -4878,7 +4816,7 @@ static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d
             if (!L.coll) {
                 // (none: every graph finished by its last k_tr_a block; pf launches: the next k_tr_a
                 // finishes this iteration, k_fx_b only after the last one)
-                if (L.blocks_fb && (!L.launch_pf || it == iters - 1)) fx_b(0, L.px_off);
+                if (L.blocks_fb && (!L.launch_pf || it == it_end - 1)) fx_b(0, L.px_off);
             } else if (L.px_on) {   // the exchange fused into k_fx_b: push in mode 1, per-block waits in mode 2
                 fx_b(1, L.px);
                 if (!L.px.spin) MR_TRY(mr_peer_fx_wait(ctx, L.px, L.blocks_fb));
@@ -4912,7 +4850,39 @@ static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d
             MR_DEBUG_CHECK(ctx, "k_iter_b");
         }
         mr_prof_end(ctx, L.bytes);
+        if (cv) {
+            mr_resid_launch(ctx, dv, ng, L.blocks_r, it, cv->max_iters, cv->resid_dev);
+            MR_DEBUG_CHECK(ctx, "k_resid");
+        }
     }
+    return MR_OK;
+}
+
+// The iterations of a convergence request: stretches of check_every iterations (one stretch of
+// max_iters when tol == 0), after each the history so far copied to the host (pinned words when
+// it fits them) with the call's only syncs before the closing one
+static int iterate_to_tol(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d, double alpha, const FxPlan& plan,
+                          const std::vector<GDev>& hv, const GDev* dv, Launch& L, Converge* cv) {
+    const size_t bytes = (size_t)ng * (size_t)cv->max_iters * sizeof(double);
+    MR_TRY_HIP(ctx, hipMemsetAsync(cv->resid_dev, 0, bytes, ctx->stream));   // (a retry overwrites the history)
+    int it = 0;
+    while (it < cv->max_iters) {
+        const int end = cv->tol > 0.0 ? std::min(it + cv->check_every, cv->max_iters) : cv->max_iters;
+        MR_TRY(iterate(ctx, gs, ng, fp32, d, alpha, it, end, plan, hv, dv, L, cv));
+        it = end;
+        if (bytes <= MR_PIN_BYTES) {
+            unsigned char* hp = nullptr;
+            MR_TRY(mr_read_bytes(ctx, cv->resid_dev, bytes, &hp));
+            memcpy(cv->resid, hp, bytes);
+        } else {
+            MR_TRY_HIP(ctx, hipMemcpyAsync(cv->resid, cv->resid_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        bool all = true;   // (a NaN residual compares false: such a graph never counts as converged)
+        for (int i = 0; i < ng; ++i) all = all && cv->resid[(size_t)i * cv->max_iters + (it - 1)] <= cv->tol;
+        if (all) break;
+    }
+    cv->iters_done = it;
     return MR_OK;
 }
 
@@ -4933,9 +4903,12 @@ static int decode_error_words(mr_ctx* ctx, const int32_t* words, const int* anom
 // One attempt with kind-hash seed `seed`; *collided reports a 64-bit key collision found by the
 // exact verification (k_kind_verify / k_sh_kind_check), after which the caller retries.
 // as: enqueue only (window groups); mr_pagerank_async_finish reads the error words
+// cv: a convergence request (iters = its max_iters; never with `as` or a sharded graph) -- no pf
+// launches: the next launch's prologue would finish an iteration and then clear the ring slot the
+// residual reads; the k_fx_b form's results are bitwise the pf form's
 static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
                             int iters, int precision, uint32_t flags, bool sharded, uint64_t seed, uint64_t hmask,
-                            bool* collided, PrAsync* as = nullptr) {
+                            bool* collided, PrAsync* as = nullptr, Converge* cv = nullptr) {
     *collided = false;
     HostMarks hm(ng);
     MR_TRY(attempt_check(ctx, gs, anomaly, ng, iters, sharded));
@@ -4946,7 +4919,7 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
     PrAsync& s = as ? *as : own;
     MR_TRY(attempt_setup(ctx, gs, anomaly, ng, d, fp32, flags, sharded, seed, hmask, s.setup_h, s.setup_d));
     hm.mark("setup");
-    const FxPlan plan = fx_plan(gs, ng, fp32, sharded);
+    const FxPlan plan = fx_plan(gs, ng, fp32, sharded, cv == nullptr);
     std::vector<int64_t> nfa;
     MR_TRY(cut_blocks(ctx, gs, ng, plan, hm, nfa));   // (marks "blocks" before its launches)
     uint64_t cold_span_all = 1;
@@ -4969,7 +4942,12 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
     MR_TRY(s.dv.upload(ctx, s.hv.data(), s.hv.size()));
     MR_TRY(prepare_exchange(ctx, gs, ng, L));
     hm.mark("pre-loop");
-    MR_TRY(iterate(ctx, gs, ng, fp32, d, alpha, iters, plan, s.hv, s.dv.p, L));
+    if (cv) {
+        MR_TRY(iterate_to_tol(ctx, gs, ng, fp32, d, alpha, plan, s.hv, s.dv.p, L, cv));
+        iters = cv->iters_done;   // (k_weights_batch: spb[iters & 1], ring slot iters % 3)
+    } else {
+        MR_TRY(iterate(ctx, gs, ng, fp32, d, alpha, 0, iters, plan, s.hv, s.dv.p, L));
+    }
     // weights of every graph and the gathered error words in one launch (the flags are final:
     // the kernels that raise them ran before the iterations; a sharded graph's words meet in a
     // MAX first, below, so it reads them after that)
@@ -5379,6 +5357,48 @@ void mr_pagerank_async_free(PrAsync* a) { delete a; }
 extern "C" int mr_pagerank_batch(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, int n_graphs, double d,
                                  double alpha, int iters, int precision, uint32_t flags) {
     return mr_pagerank_batch_impl(ctx, graphs, anomaly, n_graphs, d, alpha, iters, precision, flags);
+}
+
+// mr_pagerank_batch that records every iteration's residual and may stop at a tolerance
+// (README.md:37; pagerank.py:117's fixed count).  A kind-hash collision reruns the attempt, history included.
+extern "C" int mr_pagerank_converge(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, int n_graphs, double d,
+                                    double alpha, int max_iters, double phi, int precision, uint32_t flags, double tol,
+                                    int check_every, int32_t* iters_done, double* resid, int32_t* converged_at) {
+    if (!ctx || !graphs || !anomaly || n_graphs <= 0 || !iters_done || !resid)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: bad arguments");
+    if (max_iters < 1 || check_every < 1) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: max_iters, check_every < 1");
+    if (!(tol >= 0.0)) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: tol negative or NaN");
+    if (!(phi > 0.0)) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: phi <= 0");
+    if (flags & MR_PR_KIND_COMPRESS)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: MR_PR_KIND_COMPRESS is not supported");
+    for (int i = 0; i < n_graphs; ++i) {
+        if (!graphs[i] || graphs[i]->ctx != ctx) return mr_fail(ctx, MR_ERR_STATE, "mr_pagerank: bad handles");
+        if (graphs[i]->shard_built)
+            return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_converge: a graph of mr_graph_build_sharded is not supported");
+    }
+    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nw = (size_t)n_graphs * (size_t)max_iters;
+    DBuf<unsigned long long> rd;
+    MR_TRY(rd.alloc(ctx, nw));
+    Converge cv{tol, check_every, max_iters, rd.p, resid, 0};
+    for (int i = 0; i < n_graphs; ++i) graphs[i]->phi = phi;
+    constexpr int ATTEMPTS = 4;   // (mr_pagerank_batch_impl's seed sequence)
+    int rc = MR_OK;
+    bool collided = true;
+    for (int a = 0; a < ATTEMPTS && rc == MR_OK && collided; ++a)
+        rc = pagerank_attempt(ctx, graphs, anomaly, n_graphs, d, alpha, max_iters, precision, flags, false, kind_seed(a),
+                              kind_hmask(a), &collided, nullptr, &cv);
+    for (int i = 0; i < n_graphs; ++i) graphs[i]->phi = 0.5;
+    MR_TRY(rc);
+    if (collided) return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under %d seeds", ATTEMPTS);
+    *iters_done = cv.iters_done;
+    if (converged_at)
+        for (int i = 0; i < n_graphs; ++i) {
+            converged_at[i] = -1;
+            for (int k = 0; k < cv.iters_done && converged_at[i] < 0; ++k)
+                if (resid[(size_t)i * max_iters + k] <= tol) converged_at[i] = k + 1;
+        }
+    return MR_OK;
 }
 
 // ------------------------------------------------------------------------------ sharded graphs

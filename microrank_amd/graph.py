@@ -120,6 +120,48 @@ def host_graph_from_dicts(operation_operation: Mapping, operation_trace: Mapping
                      pr_t, pr_l)
 
 
+def check_converge_args(tol, max_iters, check_every, phi=0.5) -> None:
+    """The argument rules of mr_pagerank_converge, raised as ValueError before any library call."""
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)):
+        raise ValueError(f"tol must be a number >= 0, not {tol!r}")
+    if not float(tol) >= 0.0:   # (a NaN fails the comparison)
+        raise ValueError(f"tol must be >= 0 and not NaN, not {tol!r}")
+    for name, v in (("max_iters", max_iters), ("check_every", check_every)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, not {v!r}")
+    if not float(phi) > 0.0:
+        raise ValueError(f"phi must be > 0, not {phi!r}")
+
+
+def converge_batch(ctx, graphs, anomaly, *, tol: float, max_iters: int = 200, check_every: int = 5, d: float = 0.85,
+                   alpha: float = 0.01, phi: float = 0.5, precision: str = "fp64", exact_sums: bool = False):
+    """mr_pagerank_converge over several DeviceGraphs (anomaly: one flag per graph): the power
+    iteration with each iteration's residual max|s_k - s_{k-1}| recorded on the device, stopped at
+    the first check (every check_every iterations, and at max_iters) where every graph's last
+    residual is <= tol.  Returns one dict per graph: ``iters`` (iterations every graph ran),
+    ``residuals`` (ndarray[iters]) and ``converged_at`` (first k, 1-based, with residuals[k-1] <= tol,
+    or None).  The weights are then those of a plain ranking with ``iters`` iterations, bit for bit."""
+    check_converge_args(tol, max_iters, check_every, phi)
+    graphs, anomaly = list(graphs), [int(bool(a)) for a in anomaly]
+    if not graphs or len(graphs) != len(anomaly):
+        raise ValueError("converge_batch: one anomaly flag per graph, at least one graph")
+    lib = _lib.load()
+    n = len(graphs)
+    hs = (_lib.P * n)(*[g.h for g in graphs])
+    an = (C.c_int * n)(*anomaly)
+    prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
+    flags = _lib.MR_PR_EXACT_SUMS if exact_sums else 0
+    done = C.c_int32(0)
+    resid = np.zeros((n, int(max_iters)), np.float64)
+    conv = np.empty(n, np.int32)
+    ctx.check(lib.mr_pagerank_converge(ctx.h, hs, an, n, float(d), float(alpha), int(max_iters), float(phi), prec, flags,
+                                       float(tol), int(check_every), C.byref(done), ptr(resid, C.c_double),
+                                       ptr(conv, C.c_int32)), "mr_pagerank_converge")
+    k = int(done.value)
+    return [{"iters": k, "residuals": resid[i, :k].copy(), "converged_at": int(conv[i]) if conv[i] > 0 else None}
+            for i in range(n)]
+
+
 class DeviceGraph:
     """An mr_graph handle (HBM-resident incidence lists) plus the host-side names."""
 
@@ -170,6 +212,12 @@ class DeviceGraph:
             raise ValueError("iters must be >= 0")
         self.ctx.check(lib.mr_pagerank_ex(self.ctx.h, self.h, int(bool(anomaly)), float(d), float(alpha), int(iters),
                                           float(phi), prec, flags), "mr_pagerank_ex")
+
+    def converge(self, anomaly: bool, *, tol: float, max_iters: int = 200, check_every: int = 5, d: float = 0.85,
+                 alpha: float = 0.01, phi: float = 0.5, precision: str = "fp64", exact_sums: bool = False):
+        """Rank to a tolerance (converge_batch for this graph alone): {"iters", "residuals", "converged_at"}."""
+        return converge_batch(self.ctx, [self], [anomaly], tol=tol, max_iters=max_iters, check_every=check_every, d=d,
+                              alpha=alpha, phi=phi, precision=precision, exact_sums=exact_sums)[0]
 
     def fetch(self, kinds: bool = False):
         lib = _lib.load()

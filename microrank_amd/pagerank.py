@@ -12,10 +12,19 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .graph import DeviceGraph, host_graph_from_dicts
+from .graph import DeviceGraph, check_converge_args, host_graph_from_dicts
 
 D, ALPHA, ITERATIONS = 0.85, 0.01, 25   # pagerank.py:116-117
 PHI = 0.5                               # pagerank.py:82-84 (the anomaly preference's two 0.5s)
+MAX_ITERS = 200                         # tol= without max_iters=
+
+
+class _DefaultIters(int):
+    """The iters default: the reference's 25 as a value, recognised by identity so that an
+    explicit iters= beside tol= can be refused."""
+
+
+_ITERS_DEFAULT = _DefaultIters(ITERATIONS)
 
 
 def _device_graph(operation_operation, operation_trace, trace_operation, pr_trace, ctx):
@@ -33,16 +42,42 @@ def _device_graph(operation_operation, operation_trace, trace_operation, pr_trac
 
 
 def trace_pagerank(operation_operation, operation_trace, trace_operation, pr_trace, anomaly, *,
-                   d: float = D, alpha: float = ALPHA, iters: int = ITERATIONS, phi: float = PHI,
-                   precision: str = "fp64", ctx=None, compress_kinds: bool = False):
+                   d: float = D, alpha: float = ALPHA, iters: int = _ITERS_DEFAULT, phi: float = PHI,
+                   precision: str = "fp64", ctx=None, compress_kinds: bool = False,
+                   tol: float = None, max_iters: int = None, check_every: int = 5, info: dict = None):
     """pagerank.trace_pagerank on MI355X (pagerank.py:15-112).  The reference hard-codes d, alpha
     (pageRank's defaults, :116), the 25 iterations (:117) and phi (:82-84); they are keywords here
     with the reference's values as defaults.  compress_kinds: rank one representative per trace
-    kind with its multiplicity (same weights within fp64 rounding)."""
+    kind with its multiplicity (same weights within fp64 rounding).
+
+    tol: iterate until max|s_k - s_{k-1}| <= tol instead of a fixed count (the reference's README
+    asks for more iterations on large systems), looked at every check_every iterations and at
+    max_iters (default 200); a dict passed as info receives ``iters``, ``residuals`` and
+    ``converged_at`` (DeviceGraph.converge).  Not together with iters= or compress_kinds."""
+    if tol is None:
+        if max_iters is not None:
+            raise ValueError("max_iters needs tol (a fixed count is iters=)")
+        iters = int(iters)
+    else:
+        if iters is not _ITERS_DEFAULT:
+            raise ValueError("iters= and tol= exclude each other: with tol the count is max_iters")
+        if compress_kinds:
+            raise ValueError("tol= with compress_kinds=True is not supported: mr_pagerank_converge has no "
+                             "kind-compressed form (MR_PR_KIND_COMPRESS)")
+        max_iters = MAX_ITERS if max_iters is None else max_iters
+        check_converge_args(tol, max_iters, check_every, phi)
+        if info is not None and not isinstance(info, dict):
+            raise ValueError("info must be a dict (or None)")
     ctx = ctx or _lib.default_context()
     g, owned = _device_graph(operation_operation, operation_trace, trace_operation, pr_trace, ctx)
     try:
-        g.pagerank(bool(anomaly), d, alpha, iters, precision, compress_kinds=compress_kinds, phi=phi)
+        if tol is None:
+            g.pagerank(bool(anomaly), d, alpha, iters, precision, compress_kinds=compress_kinds, phi=phi)
+        else:
+            rep = g.converge(bool(anomaly), tol=tol, max_iters=max_iters, check_every=check_every, d=d, alpha=alpha,
+                             phi=phi, precision=precision)
+            if info is not None:
+                info.update(rep)
         w, cov = g.fetch()
     finally:
         if owned:
@@ -55,4 +90,3 @@ def trace_pagerank(operation_operation, operation_trace, trace_operation, pr_tra
     for i, op in enumerate(nodes):
         weight[op] = np.float64(w[i])
     return weight, trace_num_list
-
