@@ -135,10 +135,11 @@ int mr_pagerank_batch(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, 
  * Contract: after a call that ran K = *iters_done iterations, every graph's weights and coverage
  * (mr_graph_fetch) are bitwise those of mr_pagerank_batch(..., iters = K, ...) on the same graphs.
  * MR_ERR_ARG: null pointers (converged_at may be NULL), n_graphs < 1, max_iters < 1,
- * check_every < 1, tol negative or NaN, phi <= 0 -- and the three forms this entry does not cover:
- * MR_PR_KIND_COMPRESS, a graph built by mr_graph_build_sharded (an early stop must be agreed over
- * the ranks; mr_pagerank_sharded takes a count), and window batches (mr_windows_batch and
- * mr_rca_window rank with their fixed count and have no convergence form).  Everything else as
+ * check_every < 1, tol negative or NaN, phi <= 0 -- and the two forms this entry does not cover:
+ * MR_PR_KIND_COMPRESS and a graph built by mr_graph_build_sharded (an early stop must be agreed
+ * over the ranks; mr_pagerank_sharded takes a count).  Window batches build their graphs inside
+ * the call, so they have entries of their own: mr_windows_batch_ex and mr_rca_window_ex take a
+ * count, report the last iteration's residual and stop at a tolerance.  Everything else as
  * mr_pagerank_batch: its errors, the kind-hash collision retry (which reruns the attempt and
  * overwrites the history), mr_graph_fetch afterwards. */
 int mr_pagerank_converge(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, int n_graphs,
@@ -329,6 +330,49 @@ int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* span
                      const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid, int method,
                      int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
                      int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status);
+
+/* mr_windows_batch with a caller-chosen iteration count, a convergence report per window and an
+ * optional stop at a tolerance.  The reference ranks every window with 25 iterations
+ * (pagerank.py:117) and its README's production notices say a large system "needs more iterations
+ * in PageRank" (README.md:37); mr_windows_batch(...) is mr_windows_batch_ex(..., 25, 0.0, 1, NULL,
+ * NULL), launch for launch.  Every argument of mr_windows_batch in its order, then:
+ *   iters        tol == 0: every ranked window's two graphs run exactly iters iterations, through
+ *                mr_windows_batch's pipeline.  tol > 0: the maximum.
+ *   tol          > 0: the graphs of a group of windows (the windows whose PageRanks share launches)
+ *                are ranked by mr_pagerank_converge's attempt and stop at the first check -- every
+ *                check_every iterations, and at iters -- where every graph of the group is <= tol.
+ *                That ranking is synchronous: the next group's iterations no longer queue behind
+ *                this group's, and a call of one chunk runs its spectrum after the words are read;
+ *                this lost overlap is the price of tol.  With MR_FP32 residuals bottom out near
+ *                6e-8: a smaller tol runs to iters.
+ *   check_every  tol > 0 only (ignored otherwise, but checked).
+ *   iters_done   [n_windows] host or NULL: iterations window i's graphs ran; 0 for a window that
+ *                ranked nothing (an empty window, status MR_ERR_VALUE, or a window without abnormal
+ *                or without normal traces).  Windows of one group report the same count.
+ *   resid        [2 * n_windows] host or NULL: resid[2i] the residual max over ops of
+ *                | s_k - s_{k-1} | (mr_pagerank_converge's, k = iters_done[i]) of the last
+ *                iteration run by the graph of the detector's abnormal traces (ranked with
+ *                anomaly = 0, T1), resid[2i + 1] that of the graph of its normal traces
+ *                (anomaly = 1); 0.0 for a window that ranked nothing.
+ * edges_traversed[i] counts iters_done[i] iterations.  With both report pointers NULL no residual
+ * kernel is launched and nothing extra is copied; with one, a fixed-count call adds one k_resid
+ * launch per group behind its last iteration, read with the group's error words.
+ * Contract: window i's top list and scores are bitwise those of a fixed-count call (tol = 0) with
+ * iters = iters_done[i], whatever the grouping of the windows.  A kind-hash collision rerun keeps
+ * iters / tol and overwrites the report.
+ * MR_ERR_ARG: iters < 1, check_every < 1, tol negative or NaN, and mr_windows_batch's. */
+int mr_windows_batch_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                        const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid, int method,
+                        int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
+                        int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status,
+                        int iters, double tol, int check_every, int32_t* iters_done, double* resid);
+/* mr_rca_window with the same five: iters_done one word, resid two (NULL: no report).
+ * mr_rca_window(...) is mr_rca_window_ex(..., 25, 0.0, 1, NULL, NULL). */
+int mr_rca_window_ex(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* a3,
+                     const uint8_t* a3_valid, int method, int32_t top_max, int precision,
+                     int32_t* out_podop, double* out_score, int32_t* n_out, int64_t* edges_traversed,
+                     int32_t* n_abnormal, int32_t* n_normal, int iters, double tol, int check_every,
+                     int32_t* iters_done, double* resid);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the

@@ -9,6 +9,12 @@
 // is the L-infinity distance between the vectors the reference holds in `s` after it+1 and after
 // `it` iterations (pagerank.py:126; s_0 is the unnormalised 1/(N+T) of :118, M_s(0) = 1).  A max
 // needs no op order: relabelled graphs are read as they lie.  spb is fp64 in both precisions.
+//
+// A history (mr_pagerank_converge, the window entries' tol form) runs it after every iteration, which
+// rules out pf launches.  The report of a fixed count runs it once, after the LAST iteration, in any
+// launch form: launch K-1 cleared slot (K+1)%3, a pf launch's block 0 published s_{K-1} and M_s(K-1)
+// to spb[(K-1)&1] and slot (K-1)%3 in its prologue, the closing k_fx_b (or the last block's finish)
+// wrote spb[K&1] and slot K%3, and nothing runs after them (K = 1: the set-up's s_0, M_s(0) = 1).
 #include "mr_iter_dev.h"
 #include "mr_prim.h"
 
@@ -27,8 +33,8 @@ __device__ __forceinline__ int32_t resid_graph_of(const GDev* gs, int32_t ng, in
     return lo;
 }
 
-__global__ void __launch_bounds__(RESID_T) k_resid(const GDev* __restrict__ gs, int32_t ng, int it, int max_iters,
-                                                   unsigned long long* __restrict__ resid) {
+__global__ void __launch_bounds__(RESID_T) k_resid(const GDev* __restrict__ gs, int32_t ng, int it, int stride, int slot,
+                                                   int store, unsigned long long* __restrict__ resid) {
     __shared__ double red[RESID_T / WAVE];
     const int32_t gi = resid_graph_of(gs, ng, (int32_t)blockIdx.x);
     const GDev& G = gs[gi];
@@ -61,10 +67,14 @@ __global__ void __launch_bounds__(RESID_T) k_resid(const GDev* __restrict__ gs, 
     m = block_max(m, red);
     // non-negative doubles (and a NaN, sign cleared by fabs) order as their bit patterns: an
     // integer max, so the word does not depend on the blocks' arrival order
-    if (threadIdx.x == 0) atomicMax(&resid[(size_t)gi * max_iters + it], d2bits(m));
+    // store: every graph of the launch is one block, which writes its word (no zeroing before it)
+    if (threadIdx.x == 0) {
+        if (store) resid[(size_t)gi * stride + slot] = d2bits(m);
+        else atomicMax(&resid[(size_t)gi * stride + slot], d2bits(m));
+    }
 }
 
-void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int max_iters,
+void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int stride, int slot, bool store,
                      unsigned long long* resid) {
-    hipLaunchKernelGGL(k_resid, dim3(blocks), dim3(RESID_T), 0, ctx->stream, dv, ng, it, max_iters, resid);
+    hipLaunchKernelGGL(k_resid, dim3(blocks), dim3(RESID_T), 0, ctx->stream, dv, ng, it, stride, slot, store ? 1 : 0, resid);
 }

@@ -297,6 +297,8 @@ struct WinRun {
     int64_t nin = 0;
     mr_graph *gn = nullptr, *ga = nullptr;   // "normal" graph (detector's abnormal traces), "anomaly" graph
     bool slot = false;                       // batch: its spectrum went to the device result slot
+    int32_t iters = 0;                       // iterations its graphs ran (0: nothing ranked)
+    double resid[2] = {0.0, 0.0};            // the last iteration's residual of gn, ga (when asked for)
     ~WinRun() {
         delete gn;
         delete ga;
@@ -642,25 +644,44 @@ static int win_spectrum(mr_ctx* ctx, const mr_spans* s, const WinRun& w, int met
 }
 
 static int64_t win_edges(const WinRun& w) {
-    return w.gn ? 25 * (2 * (w.gn->nnz_sr + w.ga->nnz_sr) + w.gn->E + w.ga->E) : 0;
+    return w.gn ? (int64_t)w.iters * (2 * (w.gn->nnz_sr + w.ga->nnz_sr) + w.gn->E + w.ga->E) : 0;
+}
+
+// the count, tolerance and check interval of the _ex entries (the rules of mr_pagerank_converge)
+static int win_iter_args(mr_ctx* ctx, const char* fn, int iters, double tol, int check_every) {
+    if (iters < 1 || check_every < 1) return mr_fail(ctx, MR_ERR_ARG, "%s: iters, check_every < 1", fn);
+    if (!(tol >= 0.0)) return mr_fail(ctx, MR_ERR_ARG, "%s: tol negative or NaN", fn);
+    return MR_OK;
 }
 
 extern "C" int mr_rca_window(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* a3,
                              const uint8_t* a3_valid, int method, int32_t top_max, int precision, int32_t* out_podop,
                              double* out_score, int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal,
                              int32_t* n_normal) {
+    return mr_rca_window_ex(ctx, s, t0, t1, a3, a3_valid, method, top_max, precision, out_podop, out_score, n_out,
+                            edges_traversed, n_abnormal, n_normal, 25, 0.0, 1, nullptr, nullptr);   // pagerank.py:117
+}
+
+extern "C" int mr_rca_window_ex(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* a3,
+                                const uint8_t* a3_valid, int method, int32_t top_max, int precision, int32_t* out_podop,
+                                double* out_score, int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal,
+                                int32_t* n_normal, int iters, double tol, int check_every, int32_t* iters_done,
+                                double* resid) {
     if (!ctx || !s || s->ctx != ctx || !a3 || !a3_valid || !n_out) return mr_fail(ctx, MR_ERR_ARG, "mr_rca_window: bad arguments");
+    MR_TRY(win_iter_args(ctx, "mr_rca_window_ex", iters, tol, check_every));
     MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     *n_out = 0;
     if (edges_traversed) *edges_traversed = 0;
+    if (iters_done) *iters_done = 0;
+    if (resid) resid[0] = resid[1] = 0.0;
     // tables with a layout order: the window batch's build (one window), so a window ranks the
     // same whether it comes alone or in a batch (the driver's window loop and its sweep, f3)
     if (s->indexed && s->uniform_times && s->has_times && s->lo_ok && mr_lo_fits(s) && !getenv("MR_NO_LO_WIN") &&
         !getenv("MR_NO_INDEX")) {
         int32_t stw = MR_OK, na = 0, nn = 0;
         int64_t ew = 0;
-        MR_TRY(mr_windows_batch(ctx, 1, &s, &t0, &t1, &a3, &a3_valid, method, top_max, precision, out_podop, out_score,
-                                n_out, &ew, &na, &nn, &stw));
+        MR_TRY(mr_windows_batch_ex(ctx, 1, &s, &t0, &t1, &a3, &a3_valid, method, top_max, precision, out_podop, out_score,
+                                   n_out, &ew, &na, &nn, &stw, iters, tol, check_every, iters_done, resid));
         if (stw == MR_ERR_VALUE) return mr_fail(ctx, MR_ERR_VALUE, "Current span list is empty");
         if (stw != MR_OK) return stw;
         if (edges_traversed) *edges_traversed = ew;
@@ -677,9 +698,13 @@ extern "C" int mr_rca_window(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t
     if (!w.gn) return MR_OK;
     mr_graph* both[2] = {w.gn, w.ga};   // both PageRanks in one batched launch per iteration
     const int anom[2] = {0, 1};
-    MR_TRY(mr_pagerank_batch(ctx, both, anom, 2, 0.85, 0.01, 25, precision, 0));
+    // (its collision retries keep the call's count / tolerance; a retry overwrites the report)
+    MR_TRY(mr_pagerank_batch_report(ctx, both, anom, 2, 0.85, 0.01, iters, precision, tol, check_every, &w.iters,
+                                    resid ? w.resid : nullptr));
     mk.mark("pagerank");
     if (edges_traversed) *edges_traversed = win_edges(w);
+    if (iters_done) *iters_done = w.iters;
+    if (resid) memcpy(resid, w.resid, sizeof w.resid);
     MR_TRY(win_spectrum(ctx, s, w, method, top_max, out_podop, out_score, n_out));
     mk.mark("spectrum");
     return MR_OK;
@@ -722,8 +747,26 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
                                 const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid, int method,
                                 int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
                                 int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status) {
+    return mr_windows_batch_ex(ctx, n_windows, spans, t0, t1, a3, a3_valid, method, top_max, precision, out_podop,
+                               out_score, n_out, edges_traversed, n_abnormal, n_normal, status, 25, 0.0, 1, nullptr,
+                               nullptr);   // pagerank.py:117
+}
+
+// iters / tol / check_every, iters_done / resid: include/microrank_hip.h.  tol == 0: the pipeline
+// below with `iters` for the reference's 25 and, when a report is asked for, one k_resid per group
+// behind its last iteration, read with the group's error words.  tol > 0: every group ranked
+// synchronously by the convergence attempt (mr_pagerank_batch_report), the way a collision rerun
+// ranks one; no early spectra.
+extern "C" int mr_windows_batch_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                                   const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid, int method,
+                                   int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
+                                   int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status,
+                                   int iters, double tol, int check_every, int32_t* iters_done, double* resid) {
     if (!ctx || n_windows < 0 || (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !n_out || !status)))
         return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch: bad arguments");
+    MR_TRY(win_iter_args(ctx, "mr_windows_batch_ex", iters, tol, check_every));
+    const bool report = iters_done || resid;   // (none: no residual kernel, no words beside the error words)
+    const bool to_tol = tol > 0.0;
     for (int32_t i = 0; i < n_windows; ++i)
         if (!spans[i] || spans[i]->ctx != ctx || !a3[i] || !a3_valid[i])
             return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch: bad window %d", i);
@@ -967,7 +1010,8 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
     // read one group later; only then are its spectra queued (a kind-hash collision reruns the
     // group synchronously first).
     {
-        const size_t need = (size_t)8 * n_windows;   // 4 words per graph, 2 graphs per window
+        // 4 words per graph, 2 graphs per window; a report: a residual (2 words) per graph behind them
+        const size_t need = (size_t)(report ? 12 : 8) * n_windows;
         if (ctx->pin_flags_n < need) {
             if (ctx->pin_flags) (void)hipHostFree(ctx->pin_flags);
             ctx->pin_flags = nullptr;
@@ -981,6 +1025,16 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
     std::vector<PrAsync*> pend((size_t)ngroups, nullptr);
     std::vector<std::vector<mr_graph*>> ggs((size_t)ngroups);
     std::vector<std::vector<int>> gan((size_t)ngroups);
+    std::vector<std::vector<int32_t>> gwin((size_t)ngroups);   // a group's ranked windows: graphs 2k, 2k + 1 of ggs
+    // the iterations a group's graphs ran and, with a report, their last residuals (rs: a graph each)
+    auto ranked = [&](int g, int32_t done, const double* rs) {
+        const std::vector<int32_t>& wi = gwin[(size_t)g];
+        for (size_t k = 0; k < wi.size(); ++k) {
+            WinRun& r = w[(size_t)wi[k]];
+            r.iters = done;
+            if (rs) memcpy(r.resid, rs + 2 * k, sizeof r.resid);
+        }
+    };
     auto record = [&](int g) -> int {
         if (!gev[(size_t)g] && hipEventCreateWithFlags(&gev[(size_t)g], hipEventDisableTiming) != hipSuccess) return MR_ERR_HIP;
         return hipEventRecord(gev[(size_t)g], pr_ctx(g)->stream) == hipSuccess ? MR_OK : MR_ERR_HIP;
@@ -1013,11 +1067,15 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
             mr_ctx* pc = pr_ctx(g);
             bool rerun = false;
             r = mr_pagerank_async_finish(pc, pend[(size_t)g], &rerun);
+            if (r == MR_OK && !rerun) ranked(g, iters, mr_pagerank_async_resid(pend[(size_t)g]));
             mr_pagerank_async_free(pend[(size_t)g]);
             pend[(size_t)g] = nullptr;
-            if (r == MR_OK && rerun) {
-                r = mr_pagerank_batch(pc, ggs[(size_t)g].data(), gan[(size_t)g].data(), (int)ggs[(size_t)g].size(), 0.85,
-                                      0.01, 25, precision, 0);
+            if (r == MR_OK && rerun) {   // (with the call's count; its report overwrites the first attempt's)
+                std::vector<double> rs(report ? ggs[(size_t)g].size() : 0);
+                int32_t done = 0;
+                r = mr_pagerank_batch_report(pc, ggs[(size_t)g].data(), gan[(size_t)g].data(), (int)ggs[(size_t)g].size(),
+                                             0.85, 0.01, iters, precision, 0.0, 1, &done, report ? rs.data() : nullptr);
+                if (r == MR_OK) ranked(g, done, report ? rs.data() : nullptr);
                 if (r == MR_OK) r = record(g);
                 reran = true;
             }
@@ -1034,7 +1092,7 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
     // (C2 one window: a ~20 us idle gap plus the spectrum's launch).  A collision rerun overwrites
     // the slots with a second round of spectra.  MR_WIN_SPEC_EARLY=0: after the words (read per call)
     const char* see = getenv("MR_WIN_SPEC_EARLY");
-    const bool spec_early = inl && !(see && atoi(see) == 0);
+    const bool spec_early = inl && !(see && atoi(see) == 0) && !to_tol;
     int settled = 0;   // groups whose spectra are queued
     // (the next group's builds run beside a group's iterations: the iterations run ~20 % slower
     // than alone, but a call that builds every window before the first iterations ranked 3.5 %
@@ -1063,12 +1121,22 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
                 gs.push_back(r.ga);
                 anom.push_back(0);
                 anom.push_back(1);
+                gwin[(size_t)g].push_back(i);
             }
         }
-        if (!gs.empty()) {
+        if (!gs.empty() && to_tol) {   // synchronous, as a collision rerun: the documented price of tol
             WinPhase ph(6);
-            rc = mr_pagerank_batch_async(pc, gs.data(), anom.data(), (int)gs.size(), 0.85, 0.01, 25, precision,
-                                         ctx->pin_flags + (size_t)8 * i0, &pend[(size_t)g], spec_early);
+            std::vector<double> rs(report ? gs.size() : 0);
+            int32_t done = 0;
+            rc = mr_pagerank_batch_report(pc, gs.data(), anom.data(), (int)gs.size(), 0.85, 0.01, iters, precision, tol,
+                                          check_every, &done, report ? rs.data() : nullptr);
+            if (rc == MR_OK) ranked(g, done, report ? rs.data() : nullptr);
+            if (rc != MR_OK && pc != ctx) ctx->err = pc->err;
+        } else if (!gs.empty()) {
+            WinPhase ph(6);
+            rc = mr_pagerank_batch_async(pc, gs.data(), anom.data(), (int)gs.size(), 0.85, 0.01, iters, precision,
+                                         ctx->pin_flags + (size_t)(report ? 12 : 8) * i0, &pend[(size_t)g], spec_early,
+                                         report);
             if (rc != MR_OK && pc != ctx) ctx->err = pc->err;
         }
         // (early spectra: they follow on this stream, so no event between them and the iterations;
@@ -1157,6 +1225,8 @@ extern "C" int mr_windows_batch(mr_ctx* ctx, int32_t n_windows, const mr_spans* 
         const WinRun& r = w[(size_t)i];
         status[i] = r.rc;
         if (edges_traversed) edges_traversed[i] = r.rc == MR_OK ? win_edges(r) : 0;
+        if (iters_done) iters_done[i] = r.iters;
+        if (resid) memcpy(resid + 2 * (size_t)i, r.resid, sizeof r.resid);
         if (n_abnormal) n_abnormal[i] = r.na;
         if (n_normal) n_normal[i] = r.nn;
     }

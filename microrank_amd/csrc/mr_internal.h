@@ -491,13 +491,26 @@ int mr_ix_launch2(mr_ctx* ctx, const mr_spans* sp, const uint8_t* d_state, mr_gr
 // alive in the handle; finish waits for it and reports a kind-hash collision (rerun with the
 // synchronous batch) or an error.  hflag: 4 * ng pinned words.  defer: the error words' copy and
 // the finish's event are left for mr_pagerank_async_commit (the caller enqueues work that needs no
-// words first -- a single window's spectrum -- so no event sits between it and the iterations)
+// words first -- a single window's spectrum -- so no event sits between it and the iterations).
+// report (iters >= 1): one k_resid launch behind the last iteration; hflag then holds 6 * ng words,
+// 8-byte aligned, the graphs' residuals of that iteration (doubles) behind the error words in the
+// same copy -- mr_pagerank_async_resid after the finish ([ng], inside hflag; null without a report)
 struct PrAsync;
 int mr_pagerank_batch_async(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
-                            int iters, int precision, int32_t* hflag, PrAsync** out, bool defer = false);
+                            int iters, int precision, int32_t* hflag, PrAsync** out, bool defer = false,
+                            bool report = false);
 int mr_pagerank_async_commit(mr_ctx* ctx, PrAsync* a);
 int mr_pagerank_async_finish(mr_ctx* ctx, PrAsync* a, bool* rerun);
+const double* mr_pagerank_async_resid(const PrAsync* a);
 void mr_pagerank_async_free(PrAsync* a);
+// A group's graphs ranked synchronously (flags 0), kind-hash collision retries included.  tol == 0:
+// mr_pagerank_batch with `iters` iterations, resid ([ng] host, or null: none asked, no launch for
+// it) the residual of the last one.  tol > 0: the convergence attempt of mr_pagerank_converge with
+// max_iters = iters (k_fx_b every iteration, the history read every check_every), stopped at the
+// first check where every graph is <= tol; resid the residuals of the last iteration run.
+// *iters_done: the iterations every graph ran.
+int mr_pagerank_batch_report(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
+                             int iters, int precision, double tol, int check_every, int32_t* iters_done, double* resid);
 int mr_ix_launch2_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, uint8_t* const* d_states, mr_graph* const* g0s,
                         mr_graph* const* g1s, IxBuild* const* b0s, IxBuild* const* b1s, int64_t* const* d_outs,
                         const DetIn* dets, bool fuse);

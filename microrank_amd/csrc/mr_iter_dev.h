@@ -87,9 +87,11 @@ struct GDev {
 };
 
 // The convergence residual (mr_converge.hip): after iteration `it` of a launch's ng graphs,
-// resid[g * max_iters + it] = bits of max_o |spb[(it+1)&1][o] / M_s(it+1) - spb[it&1][o] / M_s(it)|,
-// one block per RESID_OPS ops of a graph (GDev::blk0r; `blocks` over the launch).  The words are
-// zero before the loop (an integer max of non-negative doubles' bits: order-free).
+// resid[g * stride + slot] = bits of max_o |spb[(it+1)&1][o] / M_s(it+1) - spb[it&1][o] / M_s(it)|,
+// one block per RESID_OPS ops of a graph (GDev::blk0r; `blocks` over the launch).  A history takes
+// stride = max_iters, slot = it; a report of the last iteration alone stride 1, slot 0 (one word
+// per graph).  The words are zero before the launch (an integer max of non-negative doubles'
+// bits: order-free) -- or, store: every graph is one block (blocks == ng), which stores its word.
 constexpr int32_t RESID_OPS = 4096;
-void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int max_iters,
+void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int stride, int slot, bool store,
                      unsigned long long* resid);

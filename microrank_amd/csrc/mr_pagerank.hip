@@ -4419,7 +4419,8 @@ struct PrAsync {
     DBuf<GDev> dv;
     DBuf<int32_t> fl;
     hipEvent_t ev = nullptr;
-    int32_t* hflag = nullptr;   // pinned, 4 per graph
+    int32_t* hflag = nullptr;   // pinned, 4 per graph (6 with a report: the residuals' words behind them)
+    bool report = false;        // the last iteration's residual of every graph travels with the words
     std::vector<int> anomaly;
     int ng = 0;
     bool defer = false;         // the words' copy waits for mr_pagerank_async_commit
@@ -4851,7 +4852,7 @@ static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d
         }
         mr_prof_end(ctx, L.bytes);
         if (cv) {
-            mr_resid_launch(ctx, dv, ng, L.blocks_r, it, cv->max_iters, cv->resid_dev);
+            mr_resid_launch(ctx, dv, ng, L.blocks_r, it, cv->max_iters, it, false, cv->resid_dev);
             MR_DEBUG_CHECK(ctx, "k_resid");
         }
     }
@@ -4906,9 +4907,12 @@ static int decode_error_words(mr_ctx* ctx, const int32_t* words, const int* anom
 // cv: a convergence request (iters = its max_iters; never with `as` or a sharded graph) -- no pf
 // launches: the next launch's prologue would finish an iteration and then clear the ring slot the
 // residual reads; the k_fx_b form's results are bitwise the pf form's
+// last_resid ([ng] host; as: as->report): the residual of the last iteration alone, one k_resid
+// behind the iterations, in every launch form -- nothing runs after the closing k_fx_b, so the ring
+// slots and both vectors it reads are intact; its words share the error words' read
 static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
                             int iters, int precision, uint32_t flags, bool sharded, uint64_t seed, uint64_t hmask,
-                            bool* collided, PrAsync* as = nullptr, Converge* cv = nullptr) {
+                            bool* collided, PrAsync* as = nullptr, Converge* cv = nullptr, double* last_resid = nullptr) {
     *collided = false;
     HostMarks hm(ng);
     MR_TRY(attempt_check(ctx, gs, anomaly, ng, iters, sharded));
@@ -4952,8 +4956,17 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
     // the kernels that raise them ran before the iterations; a sharded graph's words meet in a
     // MAX first, below, so it reads them after that)
     DBuf<int32_t>& fl = s.fl;
-    MR_TRY(fl.alloc(ctx, (size_t)4 * ng));
+    const bool report = !cv && !sharded && iters >= 1 && (as ? as->report : last_resid != nullptr);
+    const size_t nwords = (size_t)(report ? 6 : 4) * ng;   // (a report: 8-byte residual words behind the error words)
+    MR_TRY(fl.alloc(ctx, nwords));
     hm.mark("loop");
+    if (report) {
+        unsigned long long* rw = (unsigned long long*)(fl.p + (size_t)4 * ng);
+        const bool one_block = L.blocks_r == ng;   // (window graphs: N <= RESID_OPS) each block stores its word
+        if (!one_block) MR_TRY_HIP(ctx, hipMemsetAsync(rw, 0, (size_t)ng * sizeof(unsigned long long), st));
+        mr_resid_launch(ctx, s.dv.p, ng, L.blocks_r, iters - 1, 1, 0, one_block, rw);
+        MR_DEBUG_CHECK(ctx, "k_resid");
+    }
     hipLaunchKernelGGL(k_weights_batch, dim3(ng), dim3(1024), 0, st, s.dv.p, iters,
                        (int)((flags & MR_PR_EXACT_SUMS) != 0), fl.p);
     MR_DEBUG_CHECK(ctx, "k_weights_batch");
@@ -4970,15 +4983,16 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
         return as->defer ? MR_OK : mr_pagerank_async_commit(ctx, as);
     }
     // the only host round trip of the call: error words raised by the kernels (one pinned read)
-    std::vector<int32_t> hflag((size_t)4 * ng, 0);
-    if ((size_t)4 * ng * sizeof(int32_t) <= MR_PIN_BYTES) {
+    std::vector<int32_t> hflag(nwords, 0);
+    if (nwords * sizeof(int32_t) <= MR_PIN_BYTES) {
         unsigned char* hp = nullptr;
-        MR_TRY(mr_read_bytes(ctx, fl.p, (size_t)4 * ng * sizeof(int32_t), &hp));
+        MR_TRY(mr_read_bytes(ctx, fl.p, nwords * sizeof(int32_t), &hp));
         memcpy(hflag.data(), hp, hflag.size() * sizeof(int32_t));
     } else {
         MR_TRY(fl.download(ctx, hflag.data(), hflag.size()));
         MR_TRY_HIP(ctx, hipStreamSynchronize(st));
     }
+    if (report) memcpy(last_resid, hflag.data() + (size_t)4 * ng, (size_t)ng * sizeof(double));
     return decode_error_words(ctx, hflag.data(), anomaly, ng, collided);
 }
 
@@ -5178,12 +5192,12 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
 }
 
 int mr_pagerank_batch_impl(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
-                           int iters, int precision, uint32_t flags, bool sharded = false) {
+                           int iters, int precision, uint32_t flags, bool sharded = false, double* last_resid = nullptr) {
     constexpr int ATTEMPTS = 4;
     for (int a = 0; a < ATTEMPTS; ++a) {
         bool collided = false;
         MR_TRY(pagerank_attempt(ctx, gs, anomaly, ng, d, alpha, iters, precision, flags, sharded, kind_seed(a),
-                                kind_hmask(a), &collided));
+                                kind_hmask(a), &collided, nullptr, nullptr, last_resid));
         if (!collided) return MR_OK;
     }
     return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under %d seeds", ATTEMPTS);
@@ -5328,18 +5342,19 @@ extern "C" int mr_pagerank_ex(mr_ctx* ctx, mr_graph* g, int anomaly, double d, d
 }
 
 int mr_pagerank_async_commit(mr_ctx* ctx, PrAsync* a) {
-    MR_TRY_HIP(ctx, hipMemcpyAsync(a->hflag, a->fl.p, (size_t)4 * a->ng * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                   ctx->stream));
+    MR_TRY_HIP(ctx, hipMemcpyAsync(a->hflag, a->fl.p, (size_t)(a->report ? 6 : 4) * a->ng * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, ctx->stream));
     if (!a->ev) MR_TRY_HIP(ctx, hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
     MR_TRY_HIP(ctx, hipEventRecord(a->ev, ctx->stream));
     a->committed = true;
     return MR_OK;
 }
 int mr_pagerank_batch_async(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
-                            int iters, int precision, int32_t* hflag, PrAsync** out, bool defer) {
+                            int iters, int precision, int32_t* hflag, PrAsync** out, bool defer, bool report) {
     std::unique_ptr<PrAsync> a(new PrAsync());
     a->hflag = hflag;
     a->defer = defer;
+    a->report = report && iters >= 1;
     bool collided = false;
     MR_TRY(pagerank_attempt(ctx, gs, anomaly, ng, d, alpha, iters, precision, 0, false, kind_seed(0), kind_hmask(0),
                             &collided, a.get()));
@@ -5351,6 +5366,9 @@ int mr_pagerank_async_finish(mr_ctx* ctx, PrAsync* a, bool* rerun) {
     if (!a->committed) MR_TRY(mr_pagerank_async_commit(ctx, a));   // (a deferred batch nobody committed)
     MR_TRY_HIP(ctx, hipEventSynchronize(a->ev));
     return decode_error_words(ctx, a->hflag, a->anomaly.data(), a->ng, rerun);   // (a collision: the caller reruns)
+}
+const double* mr_pagerank_async_resid(const PrAsync* a) {
+    return a->report ? (const double*)(a->hflag + (size_t)4 * a->ng) : nullptr;
 }
 void mr_pagerank_async_free(PrAsync* a) { delete a; }
 
@@ -5398,6 +5416,34 @@ extern "C" int mr_pagerank_converge(mr_ctx* ctx, mr_graph* const* graphs, const 
             for (int k = 0; k < cv.iters_done && converged_at[i] < 0; ++k)
                 if (resid[(size_t)i * max_iters + k] <= tol) converged_at[i] = k + 1;
         }
+    return MR_OK;
+}
+
+// The synchronous ranking of a window group (mr_internal.h): mr_pagerank_batch with the call's count and
+// the last iteration's residuals, or the convergence attempt, whose history stays here
+int mr_pagerank_batch_report(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
+                             int iters, int precision, double tol, int check_every, int32_t* iters_done, double* resid) {
+    if (!(tol > 0.0)) {
+        MR_TRY(mr_pagerank_batch_impl(ctx, gs, anomaly, ng, d, alpha, iters, precision, 0, false, resid));
+        *iters_done = iters;
+        return MR_OK;
+    }
+    if (ng <= 0 || iters < 1 || check_every < 1) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_batch_report: bad arguments");
+    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nw = (size_t)ng * (size_t)iters;
+    DBuf<unsigned long long> rd;
+    MR_TRY(rd.alloc(ctx, nw));
+    std::vector<double> hist(nw, 0.0);
+    Converge cv{tol, check_every, iters, rd.p, hist.data(), 0};
+    constexpr int ATTEMPTS = 4;   // (mr_pagerank_batch_impl's seed sequence)
+    bool collided = true;
+    for (int a = 0; a < ATTEMPTS && collided; ++a)
+        MR_TRY(pagerank_attempt(ctx, gs, anomaly, ng, d, alpha, iters, precision, 0, false, kind_seed(a), kind_hmask(a),
+                                &collided, nullptr, &cv));
+    if (collided) return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under %d seeds", ATTEMPTS);
+    *iters_done = cv.iters_done;
+    if (resid)
+        for (int i = 0; i < ng; ++i) resid[i] = hist[(size_t)i * iters + (cv.iters_done - 1)];
     return MR_OK;
 }
 

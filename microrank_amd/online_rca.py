@@ -21,7 +21,8 @@ import pandas as pd
 from . import _lib
 from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
-from .pagerank import trace_pagerank
+from .graph import check_converge_args
+from .pagerank import ITERATIONS, trace_pagerank
 from .preprocess_data import (SpanStream, get_operation_duration_data, get_operation_slo, get_pagerank_graph,  # noqa: F401
                               get_service_operation_list, get_span, span_table)
 from .spans import to_ns
@@ -143,15 +144,15 @@ def sweep_chain(plan):
     return events
 
 
-def sweep_rank(plan, events, precision="fp64"):
-    """Every ranked window of the chain in ONE mr_windows_batch call: {m: (codes, scores, ...)}."""
+def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS):
+    """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}."""
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
     width = plan["step_n"] * plan["grain"]
     if not todo:
         return {}
     wins = [(plan["dev"], plan["t_begin"] + mm * plan["grain"], plan["t_begin"] + mm * plan["grain"] + width,
              plan["a3"], plan["ok"]) for mm in todo]
-    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision)))
+    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters)))
 
 
 def _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx):
@@ -175,12 +176,12 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
                       int(window_normal.value), int(window_abnormal.value))
 
 
-def _sweep_run(plan):
+def _sweep_run(plan, iters=ITERATIONS):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
-    _sweep_emit(plan, events, sweep_rank(plan, events))
+    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters))
 
 
 def _sweep_emit(plan, events, results):
@@ -211,25 +212,29 @@ def _sweep_emit(plan, events, results):
         _write_result(top_list, score_list)
 
 
-def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None):
+def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
 
     With trace-level window times (the renamed TraceStart/TraceEnd, online_rca.py:229-230) the
     whole sweep runs as one device detector pass, one batched ranking of the triggered windows
-    and a replay of the output (f3, :func:`_sweep_run`); otherwise window by window."""
+    and a replay of the output (f3, :func:`_sweep_run`); otherwise window by window.
+
+    iters: the PageRank iterations of every window (the reference's 25, pagerank.py:117; its README
+    asks for more on a large system)."""
+    check_converge_args(0.0, iters, 1)
     window_normal = pd.Timedelta(minutes=5)
     window_abnormal = pd.Timedelta(minutes=4)
     start = data["startTime"].min()
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan)
-    _window_loop(data, slo, operation_list, start, end)
+        return _sweep_run(plan, iters)
+    _window_loop(data, slo, operation_list, start, end, iters)
 
 
-def _window_loop(data, slo, operation_list, current_time, end):
+def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -247,9 +252,9 @@ def _window_loop(data, slo, operation_list, current_time, end):
                 current_time += window_normal
                 continue
             n_graph = get_pagerank_graph(normal_list, data)
-            normal_trace_result, normal_num_list = trace_pagerank(*n_graph, False)
+            normal_trace_result, normal_num_list = trace_pagerank(*n_graph, False, iters=iters)
             a_graph = get_pagerank_graph(abnormal_list, data)
-            anomaly_trace_result, anomaly_num_list = trace_pagerank(*a_graph, True)
+            anomaly_trace_result, anomaly_num_list = trace_pagerank(*a_graph, True, iters=iters)
             top_list, score_list = calculate_spectrum_without_delay_list(
                 anomaly_result=anomaly_trace_result, normal_result=normal_trace_result,
                 anomaly_list_len=len(abnormal_list), normal_list_len=len(normal_list), top_max=5,
@@ -270,13 +275,15 @@ class RCAStream:
     output -- prints, result.csv, the T2 TypeError -- equals the offline driver's on the
     concatenated chunks.  Spans of traces that start before the chain's next window are dropped,
     so the resident table stays a few windows long; each push re-ingests that table on the device
-    (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking."""
+    (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
+    iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
-    def __init__(self, slo, operation_list, *, ctx=None, device_append=True):
-        self.slo, self.operation_list = slo, operation_list
+    def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS):
+        check_converge_args(0.0, iters, 1)
+        self.slo, self.operation_list, self.iters = slo, operation_list, iters
         self.ctx = ctx or _lib.default_context()
         self.data = None          # retained spans as a DataFrame (host mode only)
         self.cur = None           # the chain's next window start (pd.Timestamp)
@@ -343,12 +350,12 @@ class RCAStream:
             if plan is None:   # window times vary within a trace: window by window
                 data = self._frame()
                 if final:
-                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit)
+                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
                 events = sweep_chain(plan)
-                _sweep_emit(plan, events, sweep_rank(plan, events))
+                _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters))
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -364,15 +371,36 @@ class RCAStream:
         """The window loop for per-span times, one window at a time while its start is before limit."""
         cur = self.cur
         while cur < limit:
-            nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"))
+            nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters)
             cur = nxt
         return cur
 
 
+def _iter_args(iters, tol, check_every, info, info_type):
+    """The window entries' iters / tol / check_every / info keywords, checked before any library
+    call (graph.check_converge_args' rules; iters plays max_iters).  Returns tol as the C ABI's
+    double (None: 0.0, a fixed count)."""
+    check_converge_args(0.0 if tol is None else tol, iters, check_every)
+    if info is not None and not isinstance(info, info_type):
+        raise ValueError(f"info must be a {info_type.__name__} (or None)")
+    return 0.0 if tol is None else float(tol)
+
+
+def _window_report(iters_done, resid, i):
+    return {"iters": int(iters_done[i]), "resid_normal": float(resid[2 * i]), "resid_anomaly": float(resid[2 * i + 1])}
+
+
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
-               table=None, dev=None):
-    """One RCA window entirely on the device (mr_rca_window).  Returns a dict with the top list
-    (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks."""
+               table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None):
+    """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
+    (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
+
+    iters: the PageRank iterations of both graphs (the reference's 25).  tol: stop at the first check
+    (every check_every iterations, and at iters, now the maximum) where both graphs'
+    max|s_k - s_{k-1}| is <= tol.  A dict passed as info receives ``iters`` (iterations run; 0 when
+    nothing was ranked), ``resid_normal`` and ``resid_anomaly``: the last iteration's residual of the
+    graph ranked as normal (the detector's abnormal traces, T1) and of the one ranked as anomaly."""
+    tol = _iter_args(iters, tol, check_every, info, dict)
     ctx = ctx or _lib.default_context()
     if table is None or dev is None:
         table, dev = span_table(data, ctx)
@@ -381,23 +409,36 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     codes = np.zeros(k, np.int32)
     scores = np.zeros(k, np.float64)
     n_out, na, nn, edges = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    iters_done, resid = np.zeros(1, np.int32), np.zeros(2, np.float64)
+    want = info is not None
     method = SPECTRUM_METHODS.index(spectrum_method)
     prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
-    ctx.check(_lib.load().mr_rca_window(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(a3, C.c_double),
-                                        ptr(ok, C.c_uint8), method, top_max, prec, ptr(codes, C.c_int32),
-                                        ptr(scores, C.c_double), C.byref(n_out), C.byref(edges), C.byref(na),
-                                        C.byref(nn)), "mr_rca_window")
+    ctx.check(_lib.load().mr_rca_window_ex(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(a3, C.c_double),
+                                           ptr(ok, C.c_uint8), method, top_max, prec, ptr(codes, C.c_int32),
+                                           ptr(scores, C.c_double), C.byref(n_out), C.byref(edges), C.byref(na),
+                                           C.byref(nn), int(iters), tol, int(check_every),
+                                           ptr(iters_done if want else None, C.c_int32),
+                                           ptr(resid if want else None, C.c_double)), "mr_rca_window_ex")
+    if want:
+        info.update(_window_report(iters_done, resid, 0))
     m = n_out.value
     names = table.podop_names
     return {"top": [names[c] for c in codes[:m]] if names is not None else codes[:m].tolist(),
             "score": scores[:m].tolist(), "n_abnormal": na.value, "n_normal": nn.value, "edges": edges.value}
 
 
-def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision="fp64"):
-    """C3: many RCA windows in one call (mr_windows_batch).  ``windows``: a list of
+def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision="fp64", iters=ITERATIONS, tol=None,
+                 check_every=5, info=None):
+    """C3: many RCA windows in one call (mr_windows_batch_ex).  ``windows``: a list of
     (DeviceSpans, t0_ns, t1_ns, a3, a3_valid) (the SLO arrays over the table's service-op
     codes).  Returns per window (top pod-op codes, scores, n_abnormal, n_normal, edges, status);
-    status MR_ERR_VALUE marks an empty window (the reference raises TypeError there, T2)."""
+    status MR_ERR_VALUE marks an empty window (the reference raises TypeError there, T2).
+
+    iters, tol, check_every as rca_window's; with tol the windows whose PageRanks share launches (a
+    group) stop together, and the groups are ranked one after the other instead of pipelined.  A
+    list passed as info is extended by one rca_window report per window, in order.  Each window's
+    result is bit for bit that of a fixed-count call with its reported ``iters``."""
+    tol = _iter_args(iters, tol, check_every, info, list)
     n = len(windows)
     k = max(top_max + 6, 1)
     keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
@@ -410,11 +451,17 @@ def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision
     codes = np.zeros(max(n, 1) * k, np.int32)
     scores = np.zeros(max(n, 1) * k, np.float64)
     n_out, edges, na, nn, status = (np.zeros(max(n, 1), t) for t in (np.int32, np.int64, np.int32, np.int32, np.int32))
+    iters_done, resid = np.zeros(max(n, 1), np.int32), np.zeros(2 * max(n, 1), np.float64)
+    want = info is not None
     method = SPECTRUM_METHODS.index(spectrum_method)
     prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
-    ctx.check(_lib.load().mr_windows_batch(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok, method,
-                                           top_max, prec, ptr(codes, C.c_int32), ptr(scores, C.c_double),
-                                           ptr(n_out, C.c_int32), ptr(edges, C.c_int64), ptr(na, C.c_int32),
-                                           ptr(nn, C.c_int32), ptr(status, C.c_int32)), "mr_windows_batch")
+    ctx.check(_lib.load().mr_windows_batch_ex(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok, method,
+                                              top_max, prec, ptr(codes, C.c_int32), ptr(scores, C.c_double),
+                                              ptr(n_out, C.c_int32), ptr(edges, C.c_int64), ptr(na, C.c_int32),
+                                              ptr(nn, C.c_int32), ptr(status, C.c_int32), int(iters), tol,
+                                              int(check_every), ptr(iters_done if want else None, C.c_int32),
+                                              ptr(resid if want else None, C.c_double)), "mr_windows_batch_ex")
+    if want:
+        info.extend(_window_report(iters_done, resid, i) for i in range(n))
     return [(codes[i * k:i * k + n_out[i]].copy(), scores[i * k:i * k + n_out[i]].copy(), int(na[i]), int(nn[i]),
              int(edges[i]), int(status[i])) for i in range(n)]
