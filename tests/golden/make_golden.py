@@ -312,6 +312,40 @@ def dict_general(outdir):
         json.dump(res, f, separators=(",", ":"))
 
 
+SPECTRUM_SYNTH = dict(sizes=[1, 2, 3, 65, 1025, 4097], typed=["np", "mixed", "zd_last"])
+
+
+def spectrum_synth(outdir):
+    """calculate_spectrum_without_delay_list on tests/spectrum_cases.spectrum_case inputs (tie groups
+    of hundreds, -0.0 / inf scores, Python / numpy typed weights, a late zero division): per case
+    and method the error type, or the top 11 names, their scores and each score's type.  Only the
+    seed and the results are stored; the inputs are rebuilt from integer hashes."""
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import spectrum_cases as sc
+
+    res = {"name": "spectrum_synth", "seed": sc.SEED, "no_neg_zero": list(sc.NO_NEG_ZERO), "cases": []}
+    for n in SPECTRUM_SYNTH["sizes"]:
+        for typed in SPECTRUM_SYNTH["typed"]:
+            out = {}
+            for m in sc.METHODS:
+                a_w, n_w, a_num, n_num, a_len, n_len = sc.case_for(m, n, sc.SEED, typed)
+                with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+                    try:
+                        top, score = ref_rca.calculate_spectrum_without_delay_list(
+                            anomaly_result=a_w, normal_result=n_w, anomaly_list_len=a_len, normal_list_len=n_len,
+                            top_max=5, normal_num_list=n_num, anomaly_num_list=a_num, spectrum_method=m)
+                        out[m] = {"top": list(top), "score": [fhex(s) for s in score],
+                                  "type": ["np.float64" if isinstance(s, np.float64) else type(s).__name__
+                                           for s in score]}
+                    except Exception as e:
+                        out[m] = {"error": type(e).__name__}
+            res["cases"].append({"n": n, "typed": typed, "out": out})
+    with open(os.path.join(outdir, "spectrum_synth.json"), "w") as f:
+        json.dump(res, f, separators=(",", ":"))
+    print("spectrum_synth", len(res["cases"]), "cases")
+
+
 C3_WINDOW = dict(n_ops=500, n_traces=20_000, seed=4242, branch=1.9, p_max=0.8, fault_ms=6000.0)
 
 
@@ -381,6 +415,9 @@ def main():
     if sys.argv[1:] == ["dict_general"]:
         dict_general(outdir)
         return
+    if sys.argv[1:] == ["spectrum_synth"]:
+        spectrum_synth(outdir)
+        return
     man = {"numpy": np.__version__, "pandas": pd.__version__, "python": sys.version.split()[0]}
     try:
         cfg = np.show_config(mode="dicts")
@@ -415,6 +452,7 @@ def main():
     with open(os.path.join(outdir, "dict_cases.json"), "w") as f:
         json.dump(dres, f, indent=0)
     dict_general(outdir)
+    spectrum_synth(outdir)
     # span-level: hand-built edges
     edf = edge_span_df()
     e = {}

@@ -484,8 +484,11 @@ def test_windows_batch_matches_standalone(c3_window):
 def test_window_spectrum_one_block_equals_general_path(monkeypatch):
     """k_win_spectrum (the window's union, scores, bitonic sort -- lane-exchange stages below
     stride 64 -- and top k in one block) against the general multi-launch spectrum path
-    (MR_NO_WIN_SPECTRUM_SMALL), on windows of 40 to 2500 ops (unions from a few nodes to > 2048:
-    one to four elements per thread) with top lists of 256: codes and scores bitwise equal."""
+    (MR_NO_WIN_SPECTRUM_SMALL), on windows of 40 to 2500 ops (unions of 40, 300, 687, 1451 and 2465
+    nodes: networks of 64 to 4096 keys, one to four elements per thread) with top lists of 256:
+    codes and scores bitwise equal.  In these windows the graph ranked as anomaly_result covers the
+    other one (at most 146 normal nodes, none of them normal-only) and only dstar2 runs; windows
+    with nodes on both sides, every formula and the route's limits: test_gpu_window_spectrum.py."""
     import bench
     from microrank_amd import _lib
     from microrank_amd.online_rca import rank_windows

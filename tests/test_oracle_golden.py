@@ -206,6 +206,57 @@ def test_spectrum_edge_cases():
         assert [float(x).hex() for x in score] == exp["score"]
 
 
+def test_spectrum_synth_matches_reference():
+    """oracle.spectrum against the reference's own results on the generated spectrum inputs
+    (tests/spectrum_cases.py: tie groups of hundreds, -0.0 and inf scores, Python / numpy typed
+    weights, a zero division raised by the union's last node), bit for bit: names, score hex and
+    score types of the top 11 of every method, ZeroDivisionError where the reference raised.  The
+    fixture holds results only; the inputs are rebuilt from its seed.  From here the oracle is the
+    reference of the GPU spectrum tests at every other size."""
+    import spectrum_cases as sc
+
+    fix = load_golden("spectrum_synth.json")
+    assert fix["seed"] == sc.SEED and tuple(fix["no_neg_zero"]) == sc.NO_NEG_ZERO
+    assert sorted({c["n"] for c in fix["cases"]}) == [1, 2, 3, 65, 1025, 4097]
+    assert len(fix["cases"]) == 18
+    for c in fix["cases"]:
+        assert set(c["out"]) == set(sc.METHODS)
+        for m, exp in c["out"].items():
+            case = sc.case_for(m, c["n"], fix["seed"], c["typed"])
+            if "error" in exp:
+                assert exp["error"] == "ZeroDivisionError"
+                with pytest.raises(ZeroDivisionError):
+                    sc.run_oracle(case, m, 5)
+                continue
+            top, score, _ = sc.run_oracle(case, m, 5)
+            where = (c["n"], c["typed"], m)
+            assert top == exp["top"], where
+            assert [float(s).hex() for s in score] == exp["score"], where
+            assert ["np.float64" if isinstance(s, np.float64) else type(s).__name__ for s in score] == exp["type"], where
+
+
+def test_spectrum_cases_have_their_edges():
+    """The generator's own promises (spectrum_cases.expected's assertions: the three node kinds in
+    an order of their own, no NaN for any method, inf and -0.0 scores, the typed variants) at the
+    smallest sizes and around the one-block sort's limit; tie groups of hundreds and a -0.0 inside
+    the +0.0 scores at 4096 and 4097."""
+    import spectrum_cases as sc
+
+    for n in (1, 2, 3, 5, 64, 65, 4097):
+        for typed in ("np", "mixed", "zd_last"):
+            sc.expected(n, typed)
+    kinds = set()
+    for n in (1, 2, 3):
+        a, nr = sc.spectrum_case(n)[:2]
+        kinds |= {(k in a, k in nr) for k in sc.union(sc.spectrum_case(n))}
+    assert kinds == {(True, False), (True, True), (False, True)}
+    for n in (4096, 4097):   # either side of the switch between the two sorts
+        e = sc.expected(n, "np")
+        assert sc.largest_tie_group(e["dstar2"][1]) >= 200
+        z = [bool(np.signbit(float(s))) for s in e["jaccard"][1] if float(s) == 0.0]
+        assert 0 < z.index(True) < len(z) - 1   # the -0.0 ties with the +0.0 scores: between them, by position
+
+
 @pytest.mark.parametrize("name", SPAN_CASES)
 def test_slo_and_detector_match_reference(name):
     case = load_golden(f"{name}.json")
