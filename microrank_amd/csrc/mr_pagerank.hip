@@ -2985,13 +2985,14 @@ __global__ void __launch_bounds__(WAVE * FB_W) k_fx_b(const GDev* __restrict__ g
 // cold half of each trace's su sum (pagerank.py:125), in position order: k_tr_a adds it to the
 // lane's hot sum before the division by M_s(k)
 // (over the listed wave tiles only: the long tiles of the general walk and the short tiles with
-// more than two cold chunks -- the short-tile walk gathers the rest itself)
+// more than two cold chunks -- the short-tile walk gathers the rest itself; tiles == nullptr: over
+// all ntl wave tiles, for a launch whose k_tr_a has no short-tile walk)
 __global__ void k_cold_trace(const int32_t* __restrict__ coff, const int32_t* __restrict__ cops,
                              const double* __restrict__ su, const int32_t* __restrict__ tiles, int32_t ntl, int32_t T,
                              double* __restrict__ cacc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)ntl * WAVE) return;
-    const int32_t p = tiles[i / WAVE] * WAVE + (int32_t)(i % WAVE);
+    const int32_t p = (tiles ? tiles[i / WAVE] : (int32_t)(i / WAVE)) * WAVE + (int32_t)(i % WAVE);
     if (p >= T) return;
     const int32_t a = coff[p], b = coff[p + 1];
     double acc = 0.0;
@@ -4542,6 +4543,7 @@ struct Launch {
     bool launch_pf = false;                 // every graph finishes in-kernel: no k_fx_b before the last iteration
     bool fb_small = false;                  // k_fx_b's block size: 4 waves
     bool coll = false, any_wide = false, px_on = false;
+    bool cold_all = false;                  // wide graphs: k_cold_trace over every tile (k_tr_a gathers no cold su)
     hipStream_t sst = nullptr;              // k_cold_ops' stream (the side stream, or the main one)
     MrPeerX px{}, px_off{};                 // the peer exchange inside k_fx_b (px_on), and none
 };
@@ -4728,6 +4730,11 @@ static int finalise_launch(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, 
             hv[(size_t)i].pf = 0;
         }
     L.tr_a = tr_kernel(fp32, plan.mode, plan.NT, any_ext == 2 && plan.w32 ? 10 : any_ext);
+    // a wide graph beside a narrow one whose su does not fit in LDS: the launch leaves WV_SU_ALL, and
+    // the kernels of the other modes have no short-tile walk (tr_kernel: no EXT variant), so none of
+    // the wide graph's tiles gathers its own cold su -- the general walk reads cold_acc for every
+    // tile, and k_cold_trace must then have summed every tile, not only the listed ones
+    L.cold_all = (any_ext & 2) && plan.mode != WV_SU_ALL;
     // a sharded graph with no collective backend is one whole shard: the split launches around the
     // (no-op) all-reduces would compute the same integers / sums in two halves
     L.coll = sharded && mr_coll_ready(ctx);
@@ -4800,10 +4807,12 @@ static int iterate(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, double d
             const size_t lds_c = (size_t)g->cold_rw * sizeof(unsigned long long);
             hipLaunchKernelGGL(cold_ops, dim3(g->n_cb), dim3(WIDE_CT), lds_c, sst, g->cb_beg.p, g->cp_pos.p, g->cp_op.p,
                                qc, g->mslot.p, it, hv[(size_t)i].cx_scale, g->cold_rw, (unsigned long long*)g->cold_part.p);
-            if (g->n_ctl)   // (the listed tiles only: the short-tile walk gathers the rest itself)
-                hipLaunchKernelGGL(k_cold_trace, dim3(cdiv((int64_t)g->n_ctl * WAVE, 256)), dim3(256), 0, st,
-                                   g->cold_off_p.p, g->cold_ops_p.p, g->sub[it & 1].p, g->ctl.p, g->n_ctl, g->T,
-                                   g->cold_acc.p);
+            // (the listed tiles only: the short-tile walk gathers the rest itself; cold_all: every tile)
+            const int32_t ntl = L.cold_all ? g->n_wt : g->n_ctl;
+            if (ntl)
+                hipLaunchKernelGGL(k_cold_trace, dim3(cdiv((int64_t)ntl * WAVE, 256)), dim3(256), 0, st,
+                                   g->cold_off_p.p, g->cold_ops_p.p, g->sub[it & 1].p,
+                                   L.cold_all ? (const int32_t*)nullptr : g->ctl.p, ntl, g->T, g->cold_acc.p);
             MR_DEBUG_CHECK(ctx, "k_cold");
         }
         if (side) MR_TRY_HIP(ctx, hipEventRecord(ctx->side_ev[1], sst));
