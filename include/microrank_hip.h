@@ -152,6 +152,26 @@ int mr_pagerank_converge(mr_ctx* ctx, mr_graph* const* graphs, const int* anomal
                                                               resid[k-1] <= tol, -1 if none; may be NULL */
 int mr_graph_fetch(mr_graph* g, double* weight /*[N] host*/, int32_t* coverage /*[N] host*/,
                    double* kind /*[T] host or NULL*/, float* pref /*[T] host or NULL*/);
+/* The trace half of the last ranking.  pageRank carries two vectors (pagerank.py:119-127): the
+ * operation vector becomes the weights, the trace vector is request_ranking_vector -- how much each
+ * trace matters under the same personalisation; the reference drops it at :130.
+ * mr_graph_trace_rank: r[t] = the max-normalised value the reference holds in
+ * request_ranking_vector[t] after the K iterations of the graph's last successful ranking
+ * (mr_pagerank, _ex, _batch; mr_pagerank_converge: the iterations it ran), in the graph's trace
+ * order (mr_graph_nodes' trace_code order, or the uploaded operation_trace order).  fp64 in both
+ * precisions; K = 0 gives 1/(N+T) for every trace (:119, un-normalised, as the reference holds it).
+ * mr_graph_exemplars: for each asked node index ops[i] the m traces with the largest r among the
+ * traces of that op's P_sr row (operation_trace, the relation `coverage` counts; pagerank.py:42-45),
+ * score descending, trace index ascending on equal values.  out_n[i] = min(m, coverage[ops[i]]);
+ * the rest of row i is padded with -1 / 0.0.  A duplicated op is answered each time.
+ * MR_ERR_ARG: null pointers, n_ops outside 1..64, m outside 1..32, an op outside [0, N).
+ * MR_ERR_STATE: no ranking yet (or its state re-set since); the last ranking was asked with
+ * MR_PR_KIND_COMPRESS (the trace vector then lives on the representatives' graph); a trace shard
+ * (mr_graph_build_sharded / mr_pagerank_sharded: each rank holds only its own traces). */
+int mr_graph_trace_rank(mr_graph* g, double* r /*[T] host*/);
+int mr_graph_exemplars(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m,
+                       int32_t* out_trace /*[n_ops*m] trace indices, -1 padded*/,
+                       double* out_score /*[n_ops*m], 0.0 padded*/, int32_t* out_n /*[n_ops]*/);
 
 /* ------------------------------------------------------------------ spans (int-coded columns)
  * The DataFrame of online_rca.py:221-248 after factorisation (microrank_amd/spans.py).

@@ -83,6 +83,8 @@ SIGNATURES = {
     "mr_pagerank_converge": (C.c_int, [P, C.POINTER(P), C.POINTER(C.c_int), C.c_int, C.c_double, C.c_double, C.c_int,
                                        C.c_double, C.c_int, C.c_uint32, C.c_double, C.c_int, i32p, f64p, i32p]),
     "mr_graph_fetch": (C.c_int, [P, f64p, i32p, f64p, f32p]),
+    "mr_graph_trace_rank": (C.c_int, [P, f64p]),
+    "mr_graph_exemplars": (C.c_int, [P, i32p, C.c_int32, C.c_int32, i32p, f64p, i32p]),
     "mr_spans_upload": (C.c_int, [P, C.POINTER(SpanCols), C.POINTER(P)]),
     "mr_graph_build_sharded": (C.c_int, [P, P, C.POINTER(C.c_uint8), C.POINTER(P)]),
     "mr_spans_free": (C.c_int, [P]),

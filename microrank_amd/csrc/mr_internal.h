@@ -315,6 +315,13 @@ struct mr_graph {
     DBuf<int32_t> slot_of;
     DBuf<uint64_t> ht_chk;   // sharded on >1 rank: check hash of each class's representative
     DBuf<int32_t> flag;          // [4] error flags written by kernels
+    // the last successful ranking of a public entry (mr_exemplar.hip reads what it left behind: q,
+    // the maxima ring, c_t); cleared by whatever re-sets the iteration state without ranking
+    bool rk_ok = false, rk_fp32 = false, rk_kc = false;   // rk_kc: asked with MR_PR_KIND_COMPRESS
+    int32_t rk_iters = 0;        // iterations run (mr_pagerank_converge: where it stopped)
+    double rk_d = 0.0;           // its damping factor
+    DBuf<double> trank;          // [T] max-normalised r of that ranking, by trace (built on first use)
+    bool trank_ok = false;
     // a window graph tiled from its table's layout order (mr_lo_prepare_batch): no trace-major
     // incidence (rs_off / rs_ops / rs16 / tperm are empty); kind counts and span counts by
     // position (kind, lo_lenp) and the preference partials (ppart) stay for a re-set-up
@@ -563,6 +570,8 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
 // such graphs together (mr_graph_prepare_batch)
 int mr_ix_finish_unprepared(mr_ctx* ctx, const mr_spans* sp, mr_graph* g, IxBuild& b, const int64_t* h);
 int mr_pagerank_presetup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, int precision, uint32_t flags);
+// mr_exemplar.hip: g->trank from the state of the last ranking (MR_ERR_STATE when there is none to read)
+int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who);
 // mr_pagerank_presetup of n graphs in six launches when all allow the batched set-up (keep: its
 // host descriptors, alive until the stream has used them)
 int mr_pagerank_presetup_n(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int n, double d, int precision,

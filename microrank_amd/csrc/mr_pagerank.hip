@@ -4461,6 +4461,7 @@ static int attempt_setup(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, i
         const bool pre = g->pre_ok && g->pre_anomaly == anomaly[i] && g->pre_d == d && g->pre_phi == g->phi && g->pre_fp32 == fp32 &&
                          g->pre_flags == flags && g->pre_seed == seed && g->pre_hmask == hmask && !sharded;
         g->pre_ok = false;   // the iteration state is consumed by this call
+        g->rk_ok = g->trank_ok = false;   // ... and the last ranking's is overwritten
         if (pre) continue;
         need.push_back(g);
         need_a.push_back(anomaly[i]);
@@ -5002,7 +5003,16 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
         MR_TRY_HIP(ctx, hipStreamSynchronize(st));
     }
     if (report) memcpy(last_resid, hflag.data() + (size_t)4 * ng, (size_t)ng * sizeof(double));
-    return decode_error_words(ctx, hflag.data(), anomaly, ng, collided);
+    MR_TRY(decode_error_words(ctx, hflag.data(), anomaly, ng, collided));
+    if (!*collided)   // what this ranking left on the device: q[iters & 1], ring slot iters % 3 (mr_exemplar.hip)
+        for (int i = 0; i < ng; ++i) {
+            gs[i]->rk_ok = true;
+            gs[i]->rk_fp32 = fp32;
+            gs[i]->rk_kc = false;
+            gs[i]->rk_iters = iters;
+            gs[i]->rk_d = d;
+        }
+    return MR_OK;
 }
 
 // A 64-bit set-hash collision between two different trace kinds is caught by the exact
@@ -5022,6 +5032,7 @@ static uint64_t kind_hmask(int a) { return (a == 0 && getenv("MR_KIND_TEST_COLLI
 // g is set up for a call with these arguments (and the first kind-hash seed): that call skips its own
 static void mark_presetup(mr_graph* g, int anomaly, double d, bool fp32, uint32_t flags) {
     g->pre_ok = true;
+    g->rk_ok = g->trank_ok = false;   // (the set-up rewrote the iteration state of the last ranking)
     g->pre_anomaly = anomaly;
     g->pre_d = d;
     g->pre_phi = g->phi;
@@ -5333,10 +5344,25 @@ static int kind_compressed_pagerank(mr_ctx* ctx, mr_graph* g, int anomaly, doubl
     return MR_OK;
 }
 
+// a ranking asked with MR_PR_KIND_COMPRESS: the trace vector lives on the representatives' graph (or,
+// for a graph that ranked uncompressed, on g -- the record says "compressed" either way: what a caller
+// may read afterwards follows from the flag it passed, not from the graph's form)
+static int kind_compressed_call(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int iters, int precision,
+                                uint32_t flags) {
+    if (g) g->rk_ok = g->trank_ok = false;
+    MR_TRY(kind_compressed_pagerank(ctx, g, anomaly, d, alpha, iters, precision, flags));
+    g->rk_ok = g->rk_kc = true;
+    g->rk_fp32 = precision == MR_FP32;
+    g->rk_iters = iters;
+    g->rk_d = d;
+    g->trank_ok = false;
+    return MR_OK;
+}
+
 extern "C" int mr_pagerank(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int iters,
                            int precision, uint32_t flags) {
     if (g) g->phi = 0.5;
-    if (flags & MR_PR_KIND_COMPRESS) return kind_compressed_pagerank(ctx, g, anomaly, d, alpha, iters, precision, flags);
+    if (flags & MR_PR_KIND_COMPRESS) return kind_compressed_call(ctx, g, anomaly, d, alpha, iters, precision, flags);
     return mr_pagerank_batch_impl(ctx, &g, &anomaly, 1, d, alpha, iters, precision, flags);
 }
 
@@ -5344,7 +5370,7 @@ extern "C" int mr_pagerank_ex(mr_ctx* ctx, mr_graph* g, int anomaly, double d, d
                               int precision, uint32_t flags) {
     if (!g || !(phi > 0.0)) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_ex: bad graph or phi");
     g->phi = phi;
-    const int rc = (flags & MR_PR_KIND_COMPRESS) ? kind_compressed_pagerank(ctx, g, anomaly, d, alpha, iters, precision, flags)
+    const int rc = (flags & MR_PR_KIND_COMPRESS) ? kind_compressed_call(ctx, g, anomaly, d, alpha, iters, precision, flags)
                                                  : mr_pagerank_batch_impl(ctx, &g, &anomaly, 1, d, alpha, iters, precision, flags);
     g->phi = 0.5;
     return rc;

@@ -133,6 +133,26 @@ def check_converge_args(tol, max_iters, check_every, phi=0.5) -> None:
         raise ValueError(f"phi must be > 0, not {phi!r}")
 
 
+EX_MAX_OPS, EX_MAX_M = 64, 32   # mr_graph_exemplars: ops per call, traces per op
+
+
+def check_exemplar_m(m) -> int:
+    """mr_graph_exemplars' m, raised as ValueError before any library call."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= EX_MAX_M:
+        raise ValueError(f"m must be an integer in 1..{EX_MAX_M}, not {m!r}")
+    return int(m)
+
+
+def check_exemplar_ops(ops) -> list:
+    """The ops of an exemplar request as a non-empty list (a lone name or index is not a list of them)."""
+    if isinstance(ops, (str, bytes)) or not hasattr(ops, "__iter__"):
+        raise ValueError(f"ops must be a sequence of node names or indices, not {ops!r}")
+    ops = list(ops)
+    if not ops:
+        raise ValueError("ops is empty")
+    return ops
+
+
 def converge_batch(ctx, graphs, anomaly, *, tol: float, max_iters: int = 200, check_every: int = 5, d: float = 0.85,
                    alpha: float = 0.01, phi: float = 0.5, precision: str = "fp64", exact_sums: bool = False):
     """mr_pagerank_converge over several DeviceGraphs (anomaly: one flag per graph): the power
@@ -228,6 +248,63 @@ class DeviceGraph:
         self.ctx.check(lib.mr_graph_fetch(self.h, ptr(w, C.c_double), ptr(cov, C.c_int32),
                                           ptr(kind, C.c_double), ptr(pref, C.c_float)), "mr_graph_fetch")
         return (w, cov, kind, pref) if kinds else (w, cov)
+
+    def trace_rank(self) -> np.ndarray:
+        """The trace half of the last ranking: ndarray[T] (float64) of what the reference holds in
+        request_ranking_vector after its iterations (pagerank.py:119-127), in this graph's trace order."""
+        r = np.empty(self.T, np.float64)
+        self.ctx.check(_lib.load().mr_graph_trace_rank(self.h, ptr(r, C.c_double)), "mr_graph_trace_rank")
+        return r
+
+    def _node_indices(self, ops) -> list:
+        index = None
+        out = []
+        for op in ops:
+            if isinstance(op, (int, np.integer)) and not isinstance(op, bool):
+                if not 0 <= op < self.N:
+                    raise ValueError(f"op index {op!r} outside [0, {self.N})")
+                out.append(int(op))
+                continue
+            if index is None:
+                index = {k: i for i, k in enumerate(self.nodes)}
+            try:
+                out.append(index[op])
+            except (KeyError, TypeError):
+                raise ValueError(f"unknown op {op!r}") from None
+        return out
+
+    def exemplars_raw(self, idx, m: int):
+        """mr_graph_exemplars for node indices (any number: calls of EX_MAX_OPS): (traces [n, m] int32,
+        -1 padded; scores [n, m]; counts [n])."""
+        lib = _lib.load()
+        n = len(idx)
+        tr = np.empty((n, m), np.int32)
+        sc = np.empty((n, m), np.float64)
+        cnt = np.empty(n, np.int32)
+        for b in range(0, n, EX_MAX_OPS):
+            ops = np.asarray(idx[b:b + EX_MAX_OPS], np.int32)
+            k = int(ops.size)
+            t, s, c = np.empty((k, m), np.int32), np.empty((k, m), np.float64), np.empty(k, np.int32)
+            self.ctx.check(lib.mr_graph_exemplars(self.h, ptr(ops, C.c_int32), k, m, ptr(t, C.c_int32),
+                                                  ptr(s, C.c_double), ptr(c, C.c_int32)), "mr_graph_exemplars")
+            tr[b:b + k], sc[b:b + k], cnt[b:b + k] = t, s, c
+        return tr, sc, cnt
+
+    def exemplars(self, ops, m: int = 5) -> dict:
+        """For each op (node names or indices) the m traces that matter most to the last ranking among
+        the traces the op occurs in (its operation_trace row): {op: [(trace, score), ...]} in request
+        order, score descending, ties by trace order; trace is the trace's name (its index on a graph
+        without names), score its entry of trace_rank()."""
+        m = check_exemplar_m(m)
+        ops = check_exemplar_ops(ops)
+        idx = self._node_indices(ops)
+        tr, sc, cnt = self.exemplars_raw(idx, m)
+        names = self.traces
+        out = {}
+        for i, op in enumerate(ops):
+            out[op] = [(names[int(t)] if names is not None else int(t), np.float64(s))
+                       for t, s in zip(tr[i, :cnt[i]], sc[i, :cnt[i]])]
+        return out
 
     def info(self):
         n, t, nnz, e = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()

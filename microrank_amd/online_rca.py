@@ -21,9 +21,9 @@ import pandas as pd
 from . import _lib
 from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
-from .graph import check_converge_args
+from .graph import check_converge_args, check_exemplar_m, check_exemplar_ops
 from .pagerank import ITERATIONS, trace_pagerank
-from .preprocess_data import (SpanStream, get_operation_duration_data, get_operation_slo, get_pagerank_graph,  # noqa: F401
+from .preprocess_data import (PagerankGraph, SpanStream, get_operation_duration_data, get_operation_slo, get_pagerank_graph,  # noqa: F401
                               get_service_operation_list, get_span, span_table)
 from .spans import to_ns
 
@@ -390,8 +390,63 @@ def _window_report(iters_done, resid, i):
     return {"iters": int(iters_done[i]), "resid_normal": float(resid[2 * i]), "resid_anomaly": float(resid[2 * i + 1])}
 
 
+def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATIONS, precision="fp64", ctx=None,
+                     table=None, dev=None):
+    """The traces to open for the ops a window's ranking names: for each pod-op of ``ops`` (names, or
+    pod-op codes) the m abnormal traces of the window that matter most to the ranking among those the
+    op occurs in -- {pod-op: [(traceID, score), ...]}, score descending.  Composed from entries that
+    exist: mr_detect -> the abnormal traces' mask -> mr_graph_build -> mr_pagerank_ex (anomaly = 0:
+    the flag the window path gives the graph of the detector's abnormal traces, T1) ->
+    mr_graph_exemplars (DeviceGraph.exemplars).  An op absent from that graph maps to []; an empty
+    window, or one without abnormal traces, returns {}."""
+    m = check_exemplar_m(m)
+    ops = check_exemplar_ops(ops)
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+        raise ValueError(f"iters must be an integer >= 0, not {iters!r}")
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    a3, ok = slo_arrays(table, slo)
+    state = np.zeros(table.n_traces, np.uint8)
+    na, nn, nin = C.c_int32(), C.c_int32(), C.c_int64()
+    rc = _lib.load().mr_detect(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(a3, C.c_double),
+                               ptr(ok, C.c_uint8), ptr(state, C.c_uint8), C.byref(na), C.byref(nn), C.byref(nin))
+    if rc == _lib.MR_ERR_VALUE and nin.value == 0:
+        return {}
+    ctx.check(rc, "mr_detect")
+    mask = state == 2
+    if not mask.any():
+        return {}
+    pg = PagerankGraph(ctx, table, dev, mask)
+    g = pg.device_graph()
+    try:
+        g.pagerank(False, iters=int(iters), precision=precision)
+        node_of = {int(c): i for i, c in enumerate(pg.node_podop)}
+        names = table.podop_names
+        code_of = {n: c for c, n in enumerate(names)} if names is not None else {}
+        idx = []
+        for op in ops:
+            code = int(op) if isinstance(op, (int, np.integer)) and not isinstance(op, bool) else code_of.get(op)
+            idx.append(node_of.get(code, -1))
+        have = [i for i in idx if i >= 0]
+        out = {op: [] for op in ops}
+        if have:
+            tr, sc, cnt = g.exemplars_raw(have, m)
+            tnames = table.trace_names
+            j = 0
+            for op, i in zip(ops, idx):
+                if i < 0:
+                    continue
+                out[op] = [(tnames[int(pg.trace_code[t])] if tnames is not None else int(pg.trace_code[t]), np.float64(s))
+                           for t, s in zip(tr[j, :cnt[j]], sc[j, :cnt[j]])]
+                j += 1
+        return out
+    finally:
+        g.close()
+
+
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
-               table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None):
+               table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -399,8 +454,14 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     (every check_every iterations, and at iters, now the maximum) where both graphs'
     max|s_k - s_{k-1}| is <= tol.  A dict passed as info receives ``iters`` (iterations run; 0 when
     nothing was ranked), ``resid_normal`` and ``resid_anomaly``: the last iteration's residual of the
-    graph ranked as normal (the detector's abnormal traces, T1) and of the one ranked as anomaly."""
+    graph ranked as normal (the detector's abnormal traces, T1) and of the one ranked as anomaly.
+
+    exemplars: an integer m adds the key ``"exemplars"``: window_exemplars for the ops of the top
+    list, with this call's iters (with tol, the iterations the report says were run).  Every other
+    key is what the call returns without the keyword."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if exemplars is not None:
+        exemplars = check_exemplar_m(exemplars)
     ctx = ctx or _lib.default_context()
     if table is None or dev is None:
         table, dev = span_table(data, ctx)
@@ -410,7 +471,7 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     scores = np.zeros(k, np.float64)
     n_out, na, nn, edges = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
     iters_done, resid = np.zeros(1, np.int32), np.zeros(2, np.float64)
-    want = info is not None
+    want = info is not None or (exemplars is not None and tol > 0.0)   # (with tol: the count for the exemplars)
     method = SPECTRUM_METHODS.index(spectrum_method)
     prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
     ctx.check(_lib.load().mr_rca_window_ex(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(a3, C.c_double),
@@ -419,12 +480,17 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
                                            C.byref(nn), int(iters), tol, int(check_every),
                                            ptr(iters_done if want else None, C.c_int32),
                                            ptr(resid if want else None, C.c_double)), "mr_rca_window_ex")
-    if want:
+    if info is not None:
         info.update(_window_report(iters_done, resid, 0))
     m = n_out.value
     names = table.podop_names
-    return {"top": [names[c] for c in codes[:m]] if names is not None else codes[:m].tolist(),
-            "score": scores[:m].tolist(), "n_abnormal": na.value, "n_normal": nn.value, "edges": edges.value}
+    res = {"top": [names[c] for c in codes[:m]] if names is not None else codes[:m].tolist(),
+           "score": scores[:m].tolist(), "n_abnormal": na.value, "n_normal": nn.value, "edges": edges.value}
+    if exemplars is not None:
+        k_run = int(iters_done[0]) if tol > 0.0 else int(iters)
+        res["exemplars"] = window_exemplars(data, start_time, end_time, slo, res["top"], m=exemplars, iters=k_run,
+                                            precision=precision, ctx=ctx, table=table, dev=dev) if m else {}
+    return res
 
 
 def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision="fp64", iters=ITERATIONS, tol=None,

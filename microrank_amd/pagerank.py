@@ -44,7 +44,8 @@ def _device_graph(operation_operation, operation_trace, trace_operation, pr_trac
 def trace_pagerank(operation_operation, operation_trace, trace_operation, pr_trace, anomaly, *,
                    d: float = D, alpha: float = ALPHA, iters: int = _ITERS_DEFAULT, phi: float = PHI,
                    precision: str = "fp64", ctx=None, compress_kinds: bool = False,
-                   tol: float = None, max_iters: int = None, check_every: int = 5, info: dict = None):
+                   tol: float = None, max_iters: int = None, check_every: int = 5, info: dict = None,
+                   trace_result: dict = None):
     """pagerank.trace_pagerank on MI355X (pagerank.py:15-112).  The reference hard-codes d, alpha
     (pageRank's defaults, :116), the 25 iterations (:117) and phi (:82-84); they are keywords here
     with the reference's values as defaults.  compress_kinds: rank one representative per trace
@@ -53,7 +54,17 @@ def trace_pagerank(operation_operation, operation_trace, trace_operation, pr_tra
     tol: iterate until max|s_k - s_{k-1}| <= tol instead of a fixed count (the reference's README
     asks for more iterations on large systems), looked at every check_every iterations and at
     max_iters (default 200); a dict passed as info receives ``iters``, ``residuals`` and
-    ``converged_at`` (DeviceGraph.converge).  Not together with iters= or compress_kinds."""
+    ``converged_at`` (DeviceGraph.converge).  Not together with iters= or compress_kinds.
+
+    trace_result: a dict passed here receives {trace name: np.float64(r)} in trace order -- the trace
+    half of the ranking, which the reference computes and drops (request_ranking_vector,
+    pagerank.py:119-127; DeviceGraph.trace_rank).  Not with compress_kinds."""
+    if trace_result is not None:
+        if not isinstance(trace_result, dict):
+            raise ValueError("trace_result must be a dict (or None)")
+        if compress_kinds:
+            raise ValueError("trace_result= with compress_kinds=True is not supported: the trace vector of a "
+                             "kind-compressed ranking (MR_PR_KIND_COMPRESS) lives on the kinds' representatives")
     if tol is None:
         if max_iters is not None:
             raise ValueError("max_iters needs tol (a fixed count is iters=)")
@@ -79,6 +90,10 @@ def trace_pagerank(operation_operation, operation_trace, trace_operation, pr_tra
             if info is not None:
                 info.update(rep)
         w, cov = g.fetch()
+        if trace_result is not None:
+            r = g.trace_rank()
+            for i, name in enumerate(g.traces if g.traces is not None else operation_trace.keys()):
+                trace_result[name] = np.float64(r[i])
     finally:
         if owned:
             g.close()
