@@ -386,6 +386,34 @@ int mr_windows_batch_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* s
                         int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
                         int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status,
                         int iters, double tol, int check_every, int32_t* iters_done, double* resid);
+/* mr_windows_batch_ex that also says WHICH TRACES: for every op of a window's top list the ex_m
+ * traces to open, read from the state the window's ranking leaves on the device before its graphs
+ * are released.  Every argument of mr_windows_batch_ex in its order, then:
+ *   ex_m       traces per op, 1..32
+ *   ex_trace   [n_windows * K * ex_m] host, K = top_max + 6: trace codes of spans[i] (the index of
+ *              mr_detect's state[]), -1 padded
+ *   ex_score   [n_windows * K * ex_m] host, 0.0 padded
+ *   ex_n       [n_windows * K] host
+ * Row (i, j) answers out_podop[i * K + j] for j < n_out[i]: the ex_m traces with the largest r_K
+ * among the traces of that pod-op's P_sr row in window i's graph of the detector's abnormal traces
+ * (the graph ranked with anomaly = 0, T1), K the iters_done[i] the window ran; r_K[t] =
+ * (q / w_t) / M_r(K) in fp64 in both precisions, mr_graph_trace_rank's expression.  Score descending
+ * by fp64 bits, trace code ascending on equal bits: the answer does not depend on how the traces
+ * are cut into blocks, on the grouping of the windows or on a window's place in the call.
+ * ex_n[i * K + j] = min(ex_m, the op's coverage in that graph); 0 for a pod-op that is no node of
+ * it (it occurs only in the detector's normal traces), for j >= n_out[i], and for a window that
+ * ranked nothing or is empty.  A kind-hash collision rerun and a tol stop answer from the final
+ * state.  Windows tiled from their table's layout order are answered by one selection launch and
+ * one merge launch for the whole call; the others through mr_graph_exemplars' kernels, a window at
+ * a time.  mr_windows_batch_ex itself is unchanged: it allocates, launches and copies nothing of this.
+ * MR_ERR_ARG: ex_m outside 1..32, a null exemplar pointer, out_podop or n_out null,
+ * top_max + 6 > 64 (mr_graph_exemplars' op limit), and mr_windows_batch_ex's. */
+int mr_windows_batch_exemplars(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                               const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                               int method, int32_t top_max, int precision, int32_t* out_podop, double* out_score,
+                               int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal,
+                               int32_t* status, int iters, double tol, int check_every, int32_t* iters_done,
+                               double* resid, int32_t ex_m, int32_t* ex_trace, double* ex_score, int32_t* ex_n);
 /* mr_rca_window with the same five: iters_done one word, resid two (NULL: no report).
  * mr_rca_window(...) is mr_rca_window_ex(..., 25, 0.0, 1, NULL, NULL). */
 int mr_rca_window_ex(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* a3,

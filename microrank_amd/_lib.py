@@ -113,6 +113,10 @@ SIGNATURES = {
     "mr_windows_batch_ex": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int, i32p, f64p, i32p, i64p, i32p,
                                       i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p]),
+    "mr_windows_batch_exemplars": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int, i32p, f64p, i32p, i64p,
+                                             i32p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p, C.c_int32, i32p,
+                                             f64p, i32p]),
     "mr_rca_window_ex": (C.c_int, [P, P, C.c_int64, C.c_int64, f64p, u8p, C.c_int, C.c_int32, C.c_int,
                                    i32p, f64p, i32p, i64p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -61,6 +61,9 @@ struct mr_ctx {
     // pinned error words of the PageRank groups a window batch has in flight (grown per call)
     int32_t* pin_flags = nullptr;
     size_t pin_flags_n = 0;
+    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars; grown per call)
+    unsigned long long* pin_ex = nullptr;
+    size_t pin_ex_n = 0;
     // one-shot peer all-reduce (mr_comm_peer_enable; mr_comm.hip): a receive region in uncached
     // device memory exported by IPC -- [flags: PEER_FLAGS u64][data: 2 parities x nranks x
     // peer_words u64] -- and every rank's region mapped into this process (peer_map[rank] = ours)
@@ -327,6 +330,9 @@ struct mr_graph {
     // position (kind, lo_lenp) and the preference partials (ppart) stay for a re-set-up
     bool lo = false;
     DBuf<int32_t> lo_lenp;       // [T] span count by position
+    // [T] by position: the trace's code in its table (lo_tr[pinv[p]]), kept only when the call asked
+    // for exemplars (mr_windows_batch_exemplars): pinv is scratch of the build
+    DBuf<int32_t> tcode;
     // [T] by position: the length of the run of identical traces (one kind class, adjacent in a
     // wave tile) a position heads, 0 for the run's other positions (k_tr_a's walk merges the run)
     DBuf<uint8_t> trun;
@@ -565,13 +571,30 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
 // their prepare and PageRank set-up (tiles, ids, kinds, preference, iteration state: pre_ok) in
 // four launches; gs[i] built from sps[i / 2] with builds bs[i]
 int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const* sps, IxBuild* const* bs,
-                        const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep);
+                        const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep,
+                        bool keep_tcode = false);   // keep_tcode: one more launch fills mr_graph.tcode
 // a graph of mr_ix_launch / mr_ix_launch2 finished WITHOUT its prepare: the caller prepares many
 // such graphs together (mr_graph_prepare_batch)
 int mr_ix_finish_unprepared(mr_ctx* ctx, const mr_spans* sp, mr_graph* g, IxBuild& b, const int64_t* h);
 int mr_pagerank_presetup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, int precision, uint32_t flags);
 // mr_exemplar.hip: g->trank from the state of the last ranking (MR_ERR_STATE when there is none to read)
 int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who);
+// mr_exemplar.hip: the exemplar rows of a window batch's ranked windows, read from the state their
+// rankings left (every stream idle, the graphs not yet released).  Window k: its graph of the
+// detector's abnormal traces g, the iterations K it ran, n_ops (<= 64, distinct) pod-op codes; its
+// rows go to trace / score [n_ops * m] and cnt [n_ops] (host).  Layout-order graphs (g->lo, tcode
+// kept) share one selection and one merge launch and one pinned read-back; the others go through
+// mr_graph_exemplars a window at a time.
+struct MrWinEx {
+    mr_graph* g;
+    int32_t K, n_ops;
+    bool fp32;
+    const int32_t* ops;
+    int32_t* trace;
+    double* score;
+    int32_t* cnt;
+};
+int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m);
 // mr_pagerank_presetup of n graphs in six launches when all allow the batched set-up (keep: its
 // host descriptors, alive until the stream has used them)
 int mr_pagerank_presetup_n(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int n, double d, int precision,

@@ -1633,6 +1633,23 @@ __global__ void __launch_bounds__(256) k_lo_fill_b(const LDev* __restrict__ ld, 
     }
     pref_partial_store(blk, a, b, G.ppart);
 }
+// (a call that asked for exemplars only) the trace code of every position, tcode[p] = lo_tr[pinv[p]]:
+// pinv leaves with the build.  One descriptor per graph, the blocks found as k_lo_apply_b's.
+struct LTDev {
+    const int32_t *pinv, *lo_tr;
+    int32_t* tcode;
+    int32_t T, b0;
+};
+__global__ void __launch_bounds__(256) k_lo_tcode_b(const LTDev* __restrict__ lt, int32_t n) {
+    int32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (lt[mid].b0 <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const LTDev& G = lt[lo];
+    const int64_t p = (int64_t)((int32_t)blockIdx.x - G.b0) * 256 + threadIdx.x;
+    if (p < G.T) G.tcode[p] = G.lo_tr[G.pinv[p]];
+}
 __global__ void __launch_bounds__(1024) k_lo_total_b(const LDev* __restrict__ ld) {   // block g: graph g
     const LDev& G = ld[blockIdx.x];
     pref_total_body(G.ppart, G.nbp, G.scal);
@@ -5116,7 +5133,8 @@ static int lo_setup_one(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp
 }
 
 int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const* sps, IxBuild* const* bs,
-                        const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep) {
+                        const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep,
+                        bool keep_tcode) {
     if (n <= 0) return MR_OK;
     const bool fp32 = precision == MR_FP32;
     hipStream_t st = ctx->stream;
@@ -5128,7 +5146,7 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
     // lane walks its own trace in its run head's order -- bitwise the merged walk
     const char* mge = getenv("MR_TR_MERGE");
     const int merge = mge ? std::min(std::max(atoi(mge), 0), 2) : 0;
-    keep.assign((size_t)n * sizeof(LDev), 0);
+    keep.assign((size_t)n * sizeof(LDev) + (keep_tcode ? (size_t)n * sizeof(LTDev) : 0), 0);
     LDev* hv = reinterpret_cast<LDev*>(keep.data());
     std::vector<DBuf<int64_t>> c64((size_t)n);
     int32_t bcs = 0, bfl = 0, bap = 0;
@@ -5208,6 +5226,26 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
     hipLaunchKernelGGL(k_lo_total_b, dim3(n), dim3(1024), 0, st, dl.p);
     hipLaunchKernelGGL(k_lo_apply_b, dim3(bap), dim3(256), 0, st, dl.p, n);
     MR_TRY_HIP(ctx, hipGetLastError());
+    if (keep_tcode) {   // the graphs ranked as "normal" (the detector's abnormal traces): the ones exemplars read
+        const size_t k0 = (size_t)n * sizeof(LDev);   // (their descriptors behind the LDevs, reserved above)
+        int nt = 0;
+        for (int i = 0; i < n; ++i) nt += anomaly[i] == 0;
+        if (nt) {
+            std::vector<LTDev> lt;
+            int32_t b0 = 0;
+            for (int i = 0; i < n; ++i) {
+                if (anomaly[i] != 0) continue;
+                MR_TRY(gs[i]->tcode.alloc(ctx, (size_t)gs[i]->T));
+                lt.push_back(LTDev{bs[i]->pinv.p, sps[i]->lo_tr.p, gs[i]->tcode.p, gs[i]->T, b0});
+                b0 += cdiv(gs[i]->T, 256);
+            }
+            memcpy(keep.data() + k0, lt.data(), lt.size() * sizeof(LTDev));
+            DBuf<LTDev> dt;
+            MR_TRY(dt.upload(ctx, reinterpret_cast<const LTDev*>(keep.data() + k0), lt.size()));
+            hipLaunchKernelGGL(k_lo_tcode_b, dim3(b0), dim3(256), 0, st, (const LTDev*)dt.p, nt);
+            MR_TRY_HIP(ctx, hipGetLastError());
+        }
+    }
     return MR_OK;   // (scratch returns to the stream-ordered pool)
 }
 

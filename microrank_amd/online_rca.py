@@ -107,6 +107,18 @@ def _write_result(top_list, score_list):
             w.writerow(["span", service, rank, float(score)])
 
 
+def _write_exemplars(top_list, score_list, rows):
+    """exemplars.csv beside result.csv: for each op of result.csv, in its order, the traces to open
+    (rows: {op: [(trace, score), ...]}, best first)."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("exemplars.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "trace", "score"])
+        for service, _ in ranked:
+            for rank, (trace, score) in enumerate(rows.get(service, []), start=1):
+                w.writerow([service, rank, trace, float(score)])
+
+
 def sweep_plan(ctx, table, dev, a3, ok, t_begin: int, t_end: int, step_normal: int, step_abnormal: int):
     """SURVEY 8(f) f3 on a resident span table: the detector counts of every window start the
     driver's chain can reach (online_rca.py:161-216: starts t_begin + m * grain while < t_end,
@@ -144,15 +156,16 @@ def sweep_chain(plan):
     return events
 
 
-def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS):
-    """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}."""
+def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None):
+    """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
+    exemplars: rank_windows' keyword (a 7th element per window)."""
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
     width = plan["step_n"] * plan["grain"]
     if not todo:
         return {}
     wins = [(plan["dev"], plan["t_begin"] + mm * plan["grain"], plan["t_begin"] + mm * plan["grain"] + width,
              plan["a3"], plan["ok"]) for mm in todo]
-    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters)))
+    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=exemplars)))
 
 
 def _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx):
@@ -176,12 +189,12 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
                       int(window_normal.value), int(window_abnormal.value))
 
 
-def _sweep_run(plan, iters=ITERATIONS):
+def _sweep_run(plan, iters=ITERATIONS, exemplars=None):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
-    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters))
+    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars))
 
 
 def _sweep_emit(plan, events, results):
@@ -201,7 +214,7 @@ def _sweep_emit(plan, events, results):
         print("total", na + nn)
         if not ranked:
             continue
-        codes, scores, r_na, r_nn, _edges, status = results[mm]
+        codes, scores, r_na, r_nn, _edges, status = results[mm][:6]
         if status != _lib.MR_OK or (r_na, r_nn) != (na, nn):
             raise RuntimeError(f"window {mm}: batch ranking disagrees with the sweep (status {status})")
         top_list = [names[c] for c in codes] if names is not None else codes.tolist()
@@ -210,9 +223,14 @@ def _sweep_emit(plan, events, results):
             print("%-50s: %.8f" % (node, sc))             # online_rca.py:151
         print(top_list, score_list)
         _write_result(top_list, score_list)
+        if len(results[mm]) > 6:   # (exemplars asked: the batch's answer, trace names where the table has them)
+            tnames = plan["table"].trace_names
+            rows = {(names[c] if names is not None else c): [(tnames[t] if tnames is not None else t, v) for t, v in lst]
+                    for c, lst in results[mm][6].items()}
+            _write_exemplars(top_list, score_list, rows)
 
 
-def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS):
+def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -222,19 +240,26 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     and a replay of the output (f3, :func:`_sweep_run`); otherwise window by window.
 
     iters: the PageRank iterations of every window (the reference's 25, pagerank.py:117; its README
-    asks for more on a large system)."""
+    asks for more on a large system).
+
+    exemplars: an integer m (1..32): every trigger also rewrites ``exemplars.csv`` beside result.csv
+    (columns result, rank, trace, score): for each op of result.csv the m abnormal traces of the
+    window to open first.  On the sweep path from the batch's own answer (rank_windows), window by
+    window from window_exemplars.  stdout and result.csv do not change; without it no file is written."""
     check_converge_args(0.0, iters, 1)
+    if exemplars is not None:
+        exemplars = check_exemplar_m(exemplars)
     window_normal = pd.Timedelta(minutes=5)
     window_abnormal = pd.Timedelta(minutes=4)
     start = data["startTime"].min()
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters)
-    _window_loop(data, slo, operation_list, start, end, iters)
+        return _sweep_run(plan, iters, exemplars)
+    _window_loop(data, slo, operation_list, start, end, iters, exemplars)
 
 
-def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS):
+def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -261,6 +286,9 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS)
                 anomaly_num_list=anomaly_num_list, normal_num_list=normal_num_list, spectrum_method="dstar2")
             print(top_list, score_list)
             _write_result(top_list, score_list)
+            if exemplars is not None:
+                rows = window_exemplars(data, start_time, end_time, slo, top_list, m=exemplars, iters=iters) if top_list else {}
+                _write_exemplars(top_list, score_list, rows)
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -276,13 +304,15 @@ class RCAStream:
     concatenated chunks.  Spans of traces that start before the chain's next window are dropped,
     so the resident table stays a few windows long; each push re-ingests that table on the device
     (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
-    iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's."""
+    iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars: its
+    keyword (exemplars.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
-    def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS):
+    def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None):
         check_converge_args(0.0, iters, 1)
+        self.exemplars = None if exemplars is None else check_exemplar_m(exemplars)
         self.slo, self.operation_list, self.iters = slo, operation_list, iters
         self.ctx = ctx or _lib.default_context()
         self.data = None          # retained spans as a DataFrame (host mode only)
@@ -350,12 +380,12 @@ class RCAStream:
             if plan is None:   # window times vary within a trace: window by window
                 data = self._frame()
                 if final:
-                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters)
+                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
                 events = sweep_chain(plan)
-                _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters))
+                _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars))
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -371,7 +401,8 @@ class RCAStream:
         """The window loop for per-span times, one window at a time while its start is before limit."""
         cur = self.cur
         while cur < limit:
-            nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters)
+            nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
+                               self.exemplars)
             cur = nxt
         return cur
 
@@ -493,8 +524,22 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     return res
 
 
+def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c):
+    """mr_windows_batch_exemplars' arrays as one {pod-op code: [(trace code, np.float64 score), ...]}
+    per window (whole-array conversions: a Python-level loop per score costs more than the device side)."""
+    cod, cnt, no, tl, sl = codes.tolist(), ex_c.tolist(), n_out.tolist(), ex_t.tolist(), list(ex_s)
+    out = []
+    for i in range(n):
+        rows = {}
+        for j in range(i * k, i * k + no[i]):
+            b = j * m
+            rows[cod[j]] = list(zip(tl[b:b + cnt[j]], sl[b:b + cnt[j]]))
+        out.append(rows)
+    return out
+
+
 def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision="fp64", iters=ITERATIONS, tol=None,
-                 check_every=5, info=None):
+                 check_every=5, info=None, exemplars=None):
     """C3: many RCA windows in one call (mr_windows_batch_ex).  ``windows``: a list of
     (DeviceSpans, t0_ns, t1_ns, a3, a3_valid) (the SLO arrays over the table's service-op
     codes).  Returns per window (top pod-op codes, scores, n_abnormal, n_normal, edges, status);
@@ -503,8 +548,17 @@ def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision
     iters, tol, check_every as rca_window's; with tol the windows whose PageRanks share launches (a
     group) stop together, and the groups are ranked one after the other instead of pipelined.  A
     list passed as info is extended by one rca_window report per window, in order.  Each window's
-    result is bit for bit that of a fixed-count call with its reported ``iters``."""
+    result is bit for bit that of a fixed-count call with its reported ``iters``.
+
+    exemplars: an integer m (1..32) makes each window's tuple carry a 7th element, read on the device
+    from what the window's ranking left (mr_windows_batch_exemplars): {pod-op code: [(trace code,
+    np.float64 score), ...]} for the codes of its top list, in top-list order -- for each the m
+    abnormal traces of the window that matter most to the ranking among those the pod-op occurs in,
+    score descending; [] for a pod-op that occurs only in the window's normal traces.  Without the
+    keyword the tuples stay 6 long, through mr_windows_batch_ex."""
     tol = _iter_args(iters, tol, check_every, info, list)
+    if exemplars is not None:
+        exemplars = check_exemplar_m(exemplars)
     n = len(windows)
     k = max(top_max + 6, 1)
     keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
@@ -521,13 +575,23 @@ def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision
     want = info is not None
     method = SPECTRUM_METHODS.index(spectrum_method)
     prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
-    ctx.check(_lib.load().mr_windows_batch_ex(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok, method,
-                                              top_max, prec, ptr(codes, C.c_int32), ptr(scores, C.c_double),
-                                              ptr(n_out, C.c_int32), ptr(edges, C.c_int64), ptr(na, C.c_int32),
-                                              ptr(nn, C.c_int32), ptr(status, C.c_int32), int(iters), tol,
-                                              int(check_every), ptr(iters_done if want else None, C.c_int32),
-                                              ptr(resid if want else None, C.c_double)), "mr_windows_batch_ex")
+    args = (ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok, method, top_max, prec, ptr(codes, C.c_int32),
+            ptr(scores, C.c_double), ptr(n_out, C.c_int32), ptr(edges, C.c_int64), ptr(na, C.c_int32), ptr(nn, C.c_int32),
+            ptr(status, C.c_int32), int(iters), tol, int(check_every), ptr(iters_done if want else None, C.c_int32),
+            ptr(resid if want else None, C.c_double))
+    if exemplars is None:
+        ctx.check(_lib.load().mr_windows_batch_ex(*args), "mr_windows_batch_ex")
+    else:
+        m = exemplars
+        ex_t = np.full(max(n, 1) * k * m, -1, np.int32)
+        ex_s = np.zeros(max(n, 1) * k * m, np.float64)
+        ex_c = np.zeros(max(n, 1) * k, np.int32)
+        ctx.check(_lib.load().mr_windows_batch_exemplars(*args, m, ptr(ex_t, C.c_int32), ptr(ex_s, C.c_double),
+                                                         ptr(ex_c, C.c_int32)), "mr_windows_batch_exemplars")
     if want:
         info.extend(_window_report(iters_done, resid, i) for i in range(n))
-    return [(codes[i * k:i * k + n_out[i]].copy(), scores[i * k:i * k + n_out[i]].copy(), int(na[i]), int(nn[i]),
-             int(edges[i]), int(status[i])) for i in range(n)]
+    out = [(codes[i * k:i * k + n_out[i]].copy(), scores[i * k:i * k + n_out[i]].copy(), int(na[i]), int(nn[i]),
+            int(edges[i]), int(status[i])) for i in range(n)]
+    if exemplars is None:
+        return out
+    return [res + (rows,) for res, rows in zip(out, _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c))]
