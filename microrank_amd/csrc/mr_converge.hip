@@ -22,21 +22,11 @@ constexpr int RESID_T = 256;                     // threads per block
 constexpr int RESID_PER = RESID_OPS / RESID_T;   // ops per thread: RESID_PER / 2 16-byte loads per vector
 static_assert(RESID_OPS % (2 * RESID_T) == 0, "a block's ops split into double2 per thread");
 
-// the graph owning block `blk` (blk0r is non-decreasing over the graphs; every graph has a block)
-__device__ __forceinline__ int32_t resid_graph_of(const GDev* gs, int32_t ng, int32_t blk) {
-    int32_t lo = 0, hi = ng - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi + 1) >> 1;
-        if (gs[mid].blk0r <= blk) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(RESID_T) k_resid(const GDev* __restrict__ gs, int32_t ng, int it, int stride, int slot,
                                                    int store, unsigned long long* __restrict__ resid) {
     __shared__ double red[RESID_T / WAVE];
-    const int32_t gi = resid_graph_of(gs, ng, (int32_t)blockIdx.x);
+    // the graph owning the block (blk0r is non-decreasing over the graphs; every graph has a block)
+    const int32_t gi = block_owner<GDev, &GDev::blk0r>(gs, ng, (int32_t)blockIdx.x);
     const GDev& G = gs[gi];
     const int32_t N = G.N;
     const double* __restrict__ sa = G.spb[(it + 1) & 1];

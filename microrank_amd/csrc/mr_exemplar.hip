@@ -352,14 +352,6 @@ struct WXDev {
     int32_t b0, nb, per;              // first block, blocks, tiles per block
     int32_t op[EX_MAXOPS];            // asked pod-op codes, distinct
 };
-__device__ __forceinline__ int32_t wx_window(const WXDev* wd, int32_t n, int32_t blk) {
-    int32_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi + 1) >> 1;
-        if (wd[mid].b0 <= blk) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 // ps / pt: [block][KO][m], padded with (0.0, -1)
 __global__ void __launch_bounds__(EX_T) k_win_ex_select(const WXDev* __restrict__ wd, int32_t nw, int32_t KO, int32_t m,
                                                         unsigned long long* __restrict__ ps, int32_t* __restrict__ pt) {
@@ -374,7 +366,7 @@ __global__ void __launch_bounds__(EX_T) k_win_ex_select(const WXDev* __restrict_
     __shared__ int32_t sop[EX_MAXOPS];
     __shared__ int32_t snc[EX_T / WAVE];
     const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    const WXDev& G = wd[wx_window(wd, nw, (int32_t)blockIdx.x)];
+    const WXDev& G = wd[block_owner<WXDev, &WXDev::b0>(wd, nw, (int32_t)blockIdx.x)];
     const int32_t N = G.N, T = G.T, K = G.K, nu = G.n_ops;
     if (tid < EX_MAXOPS) {
         lc[tid] = 0;

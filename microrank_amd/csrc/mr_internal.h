@@ -172,7 +172,7 @@ struct DBuf {
 };
 
 // Device graph: the four reference dicts as incidence lists.
-// the kinds hash table (mr_pagerank.hip): 64-bit keys in one array (the CAS-probed one, half the
+// the kinds hash table (mr_pr_kinds.hip): 64-bit keys in one array (the CAS-probed one, half the
 // footprint of a packed slot -- it stays MALL-resident longer), class size + representative in a
 // second 8 B array (one line for k_kind_verify's read)
 struct alignas(8) KCnt {

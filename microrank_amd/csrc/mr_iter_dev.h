@@ -1,5 +1,6 @@
 // What the power iteration's kernels share across translation units (mr_pagerank.hip's iteration,
-// mr_converge.hip's residual): the maxima ring and a graph's device descriptor.
+// mr_pr_setup.hip's iteration state, mr_converge.hip's residual): the maxima ring and a graph's
+// device descriptor.
 #pragma once
 #include "mr_internal.h"
 

@@ -48,6 +48,18 @@ __device__ __forceinline__ double block_max(double v, double* red) {
     return t;
 }
 
+// the descriptor owning block `blk` of a launch: FIRST is non-decreasing over ds[0..n) (descriptors
+// without blocks in the launch repeat their successor's start: the last of equal starts owns)
+template <class D, int32_t D::*FIRST>
+__device__ __forceinline__ int32_t block_owner(const D* ds, int32_t n, int32_t blk) {
+    int32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (ds[mid].*FIRST <= blk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // Exclusive scan of int64 counts: out[i] = sum(in[0..i)), out[n] = total (out has n+1 slots).
 // in == out is allowed.  Uses `tmp` device scratch of at least scan_tmp_elems(n) int64.
 int64_t scan_tmp_elems(int64_t n);
