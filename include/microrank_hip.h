@@ -172,6 +172,30 @@ int mr_graph_trace_rank(mr_graph* g, double* r /*[T] host*/);
 int mr_graph_exemplars(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m,
                        int32_t* out_trace /*[n_ops*m] trace indices, -1 padded*/,
                        double* out_score /*[n_ops*m], 0.0 padded*/, int32_t* out_n /*[n_ops]*/);
+/* mr_graph_exemplars with flags.  flags == 0 and out_mult == NULL is mr_graph_exemplars itself: the
+ * same launches and the same read-back (mr_graph_exemplars(...) is mr_graph_exemplars_ex(..., 0, ...,
+ * NULL)).  MR_EX_DISTINCT_KINDS: ONE trace per trace kind.  The kinds are the exact classes of
+ * pagerank.py:54-66 that the ranking's own set-up uses (equal operation set and equal fp32(1/len_t);
+ * exact classes, not a hash), so a kind lies wholly inside an op's P_sr row or wholly outside it.
+ * Each kind of the row is represented by its best member under mr_graph_exemplars' order (score bits
+ * descending, trace index ascending); the answer is the first min(m, kinds in the row)
+ * representatives in that same order, out_n[i] that count.  Kinds are told apart by identity, never
+ * by score: where P_rs is given apart from P_sr the members of one kind have different scores.
+ * Entry 0 is mr_graph_exemplars' entry 0; a row of singleton kinds is answered as without the flag;
+ * the answer does not depend on how the traces are cut into blocks.  K = 0: every kind by its
+ * smallest trace index, in index order.
+ * out_mult[i*m + j]: the class size of entry j, the number of traces of that kind in the graph -- the
+ * value mr_graph_fetch returns in kind[trace]; 0 padded.  May be NULL.
+ * The first call with the flag after a graph's first ranking computes the kinds' representatives once
+ * (they depend on the structure alone); it leaves mr_graph_fetch, mr_graph_trace_rank, the plain
+ * entry and the next ranking bitwise what they were.
+ * MR_ERR_ARG: a flag bit other than MR_EX_DISTINCT_KINDS, out_mult with flags == 0, and everything
+ * mr_graph_exemplars rejects.  MR_ERR_STATE: as mr_graph_exemplars (no ranking yet,
+ * MR_PR_KIND_COMPRESS, a trace shard). */
+enum { MR_EX_DISTINCT_KINDS = 1u };
+int mr_graph_exemplars_ex(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m, uint32_t flags,
+                          int32_t* out_trace, double* out_score, int32_t* out_n,
+                          int32_t* out_mult /* [n_ops*m] or NULL */);
 
 /* ------------------------------------------------------------------ spans (int-coded columns)
  * The DataFrame of online_rca.py:221-248 after factorisation (microrank_amd/spans.py).
@@ -414,6 +438,27 @@ int mr_windows_batch_exemplars(mr_ctx* ctx, int32_t n_windows, const mr_spans* c
                                int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal,
                                int32_t* status, int iters, double tol, int check_every, int32_t* iters_done,
                                double* resid, int32_t ex_m, int32_t* ex_trace, double* ex_score, int32_t* ex_n);
+/* mr_windows_batch_exemplars with mr_graph_exemplars_ex's flags: every argument of
+ * mr_windows_batch_exemplars in its order, then ex_flags and ex_mult.  ex_flags == 0 with ex_mult ==
+ * NULL is mr_windows_batch_exemplars itself (which is this call with 0, NULL): the same launches.
+ * MR_EX_DISTINCT_KINDS: row (i, j) holds one trace per trace kind of window i's graph of the
+ * detector's abnormal traces (pagerank.py:54-66's exact classes, as that graph's ranking counts
+ * them), each kind by its best member (score bits descending, trace code ascending), the first
+ * min(ex_m, kinds in the row) of them in that order; ex_n[i * K + j] is that count.
+ * ex_mult [n_windows * K * ex_m] host or NULL: the class size of every entry (the traces of that
+ * kind in the window's graph), 0 padded and 0 wherever ex_trace is -1.  The answer does not depend on
+ * the cut into blocks, on the grouping of the windows or on a window's place in the call; windows
+ * tiled from their table's layout order are still answered by one selection launch and one merge
+ * launch for the whole call (their kinds are the table's classes, kept by position only under the flag).
+ * MR_ERR_ARG: a flag bit other than MR_EX_DISTINCT_KINDS, ex_mult with ex_flags == 0, and
+ * mr_windows_batch_exemplars'.  MR_ERR_STATE: as mr_windows_batch_exemplars. */
+int mr_windows_batch_exemplars_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                                  const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                                  int method, int32_t top_max, int precision, int32_t* out_podop, double* out_score,
+                                  int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal,
+                                  int32_t* status, int iters, double tol, int check_every, int32_t* iters_done,
+                                  double* resid, int32_t ex_m, int32_t* ex_trace, double* ex_score, int32_t* ex_n,
+                                  uint32_t ex_flags, int32_t* ex_mult /* [n_windows*K*ex_m] or NULL */);
 /* mr_rca_window with the same five: iters_done one word, resid two (NULL: no report).
  * mr_rca_window(...) is mr_rca_window_ex(..., 25, 0.0, 1, NULL, NULL). */
 int mr_rca_window_ex(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* a3,

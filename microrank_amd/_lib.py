@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MR_LIB_PATH") or os.path.join(os.path.dirname(os.path
 MR_OK, MR_ERR_ARG, MR_ERR_HIP, MR_ERR_VALUE, MR_ERR_ZERODIV, MR_ERR_OOM, MR_ERR_COMM, MR_ERR_STATE = range(8)
 MR_FP64, MR_FP32 = 0, 1
 MR_PR_EXACT_SUMS = 1
+MR_EX_DISTINCT_KINDS = 1  # mr_graph_exemplars_ex / mr_windows_batch_exemplars_ex: one exemplar per trace kind
 MR_PR_KIND_COMPRESS = 2   # mr_pagerank: iterate over one representative per trace kind (§8(f) f4)
 MR_Q_LINEAR, MR_Q_LOWER, MR_Q_HIGHER = 0, 1, 2   # mr_slo_quantiles: numpy.quantile's method= names
 QUANTILE_METHODS = {"linear": MR_Q_LINEAR, "lower": MR_Q_LOWER, "higher": MR_Q_HIGHER}
@@ -85,6 +86,8 @@ SIGNATURES = {
     "mr_graph_fetch": (C.c_int, [P, f64p, i32p, f64p, f32p]),
     "mr_graph_trace_rank": (C.c_int, [P, f64p]),
     "mr_graph_exemplars": (C.c_int, [P, i32p, C.c_int32, C.c_int32, i32p, f64p, i32p]),
+    # ... then flags (MR_EX_DISTINCT_KINDS) ahead of the outputs, out_mult behind them
+    "mr_graph_exemplars_ex": (C.c_int, [P, i32p, C.c_int32, C.c_int32, C.c_uint32, i32p, f64p, i32p, i32p]),
     "mr_spans_upload": (C.c_int, [P, C.POINTER(SpanCols), C.POINTER(P)]),
     "mr_graph_build_sharded": (C.c_int, [P, P, C.POINTER(C.c_uint8), C.POINTER(P)]),
     "mr_spans_free": (C.c_int, [P]),
@@ -117,6 +120,11 @@ SIGNATURES = {
                                              C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int, i32p, f64p, i32p, i64p,
                                              i32p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p, C.c_int32, i32p,
                                              f64p, i32p]),
+    # the one above, then ex_flags, ex_mult
+    "mr_windows_batch_exemplars_ex": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int, i32p, f64p, i32p,
+                                                i64p, i32p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p,
+                                                C.c_int32, i32p, f64p, i32p, C.c_uint32, i32p]),
     "mr_rca_window_ex": (C.c_int, [P, P, C.c_int64, C.c_int64, f64p, u8p, C.c_int, C.c_int32, C.c_int,
                                    i32p, f64p, i32p, i64p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -403,7 +403,8 @@ struct WinChunk {
         if (ev) (void)hipEventDestroy(ev);
     }
 };
-static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precision, WinChunk& c, bool keep_tcode) {
+static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precision, WinChunk& c, bool keep_tcode,
+                                 bool keep_tkid) {
     hipStream_t st = ctx->stream;
     constexpr size_t CW = 3 * MR_DETECT_SHARDS;   // per window: detector counter shards, then 8 + 8 size words
     constexpr size_t WW = CW + 16;
@@ -574,7 +575,7 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
         std::vector<int> an(gs.size());
         for (size_t j = 0; j < gs.size(); ++j) an[j] = (int)(j & 1);   // (gn "normal", ga "anomaly": T1)
         if (!gs.empty()) MR_TRY(mr_lo_prepare_batch(ctx, gs.data(), gsp.data(), gbx.data(), an.data(), (int)gs.size(), 0.85,
-                                                    precision, c.keep, keep_tcode));
+                                                    precision, c.keep, keep_tcode, keep_tkid));
     } else if (!gs.empty()) {
         MR_TRY(mr_graph_prepare_batch(ctx, gs.data(), (int)gs.size(), c.keep));
     }
@@ -766,7 +767,7 @@ static int windows_batch_run(mr_ctx* ctx, int32_t n_windows, const mr_spans* con
                              int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
                              int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status,
                              int iters, double tol, int check_every, int32_t* iters_done, double* resid, int32_t ex_m,
-                             int32_t* ex_trace, double* ex_score, int32_t* ex_n) {
+                             int32_t* ex_trace, double* ex_score, int32_t* ex_n, uint32_t ex_flags, int32_t* ex_mult) {
     if (!ctx || n_windows < 0 || (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !n_out || !status)))
         return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch: bad arguments");
     MR_TRY(win_iter_args(ctx, "mr_windows_batch_ex", iters, tol, check_every));
@@ -919,7 +920,8 @@ static int windows_batch_run(mr_ctx* ctx, int32_t n_windows, const mr_spans* con
                 }
             }
             if (!fast.empty()) {
-                const int rc = win_chunk_build_async(a, fast.data(), (int)fast.size(), precision, cw[(size_t)task], ex_m > 0);
+                const int rc = win_chunk_build_async(a, fast.data(), (int)fast.size(), precision, cw[(size_t)task], ex_m > 0,
+                                                     ex_m > 0 && (ex_flags & MR_EX_DISTINCT_KINDS) != 0);
                 if (rc != MR_OK) {
                     err[(size_t)k] = a->err;
                     for (WinIn& f : fast) f.w->rc = rc;
@@ -1239,14 +1241,16 @@ static int windows_batch_run(mr_ctx* ctx, int32_t n_windows, const mr_spans* con
         std::fill(ex_trace, ex_trace + (size_t)n_windows * K * ex_m, -1);
         std::fill(ex_score, ex_score + (size_t)n_windows * K * ex_m, 0.0);
         std::fill(ex_n, ex_n + (size_t)n_windows * K, 0);
+        if (ex_mult) std::fill(ex_mult, ex_mult + (size_t)n_windows * K * ex_m, 0);
         std::vector<MrWinEx> xs;
         for (int32_t i = 0; i < n_windows; ++i) {
             const WinRun& r = w[(size_t)i];
             if (r.rc != MR_OK || !r.gn || r.iters < 1 || n_out[i] < 1) continue;
             xs.push_back(MrWinEx{r.gn, r.iters, std::min(n_out[i], K), precision == MR_FP32, out_podop + (size_t)i * K,
-                                 ex_trace + (size_t)i * K * ex_m, ex_score + (size_t)i * K * ex_m, ex_n + (size_t)i * K});
+                                 ex_trace + (size_t)i * K * ex_m, ex_score + (size_t)i * K * ex_m, ex_n + (size_t)i * K,
+                                 ex_mult ? ex_mult + (size_t)i * K * ex_m : nullptr});
         }
-        MR_TRY(mr_win_exemplars(ctx, xs.data(), (int)xs.size(), ex_m));
+        MR_TRY(mr_win_exemplars(ctx, xs.data(), (int)xs.size(), ex_m, ex_flags));
     }
     // large windows' graphs (>= 64k traces per window on average: C2) are released during the next
     // call (C2 +8 %); small windows' (C3: many graphs, many small blocks) here, on the call's exit --
@@ -1291,22 +1295,38 @@ extern "C" int mr_windows_batch_ex(mr_ctx* ctx, int32_t n_windows, const mr_span
                                    int iters, double tol, int check_every, int32_t* iters_done, double* resid) {
     return windows_batch_run(ctx, n_windows, spans, t0, t1, a3, a3_valid, method, top_max, precision, out_podop, out_score,
                              n_out, edges_traversed, n_abnormal, n_normal, status, iters, tol, check_every, iters_done,
-                             resid, 0, nullptr, nullptr, nullptr);
+                             resid, 0, nullptr, nullptr, nullptr, 0u, nullptr);
 }
 
 // include/microrank_hip.h
-extern "C" int mr_windows_batch_exemplars(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
-                                          const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
-                                          int method, int32_t top_max, int precision, int32_t* out_podop, double* out_score,
-                                          int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal,
-                                          int32_t* status, int iters, double tol, int check_every, int32_t* iters_done,
-                                          double* resid, int32_t ex_m, int32_t* ex_trace, double* ex_score, int32_t* ex_n) {
+extern "C" int mr_windows_batch_exemplars_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                                             const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                                             int method, int32_t top_max, int precision, int32_t* out_podop,
+                                             double* out_score, int32_t* n_out, int64_t* edges_traversed,
+                                             int32_t* n_abnormal, int32_t* n_normal, int32_t* status, int iters, double tol,
+                                             int check_every, int32_t* iters_done, double* resid, int32_t ex_m,
+                                             int32_t* ex_trace, double* ex_score, int32_t* ex_n, uint32_t ex_flags,
+                                             int32_t* ex_mult) {
     if (!ctx) return MR_ERR_ARG;
+    if (ex_flags & ~(uint32_t)MR_EX_DISTINCT_KINDS)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch_exemplars_ex: unknown flag bits 0x%x", ex_flags);
+    if (!ex_flags && ex_mult)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch_exemplars_ex: ex_mult without MR_EX_DISTINCT_KINDS");
     if (ex_m < 1 || ex_m > 32) return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch_exemplars: ex_m outside 1..32");
     if (!ex_trace || !ex_score || !ex_n || !out_podop || !n_out)
         return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch_exemplars: null argument");
     if (top_max + 6 > 64) return mr_fail(ctx, MR_ERR_ARG, "mr_windows_batch_exemplars: top_max + 6 > 64 ops");
     return windows_batch_run(ctx, n_windows, spans, t0, t1, a3, a3_valid, method, top_max, precision, out_podop, out_score,
                              n_out, edges_traversed, n_abnormal, n_normal, status, iters, tol, check_every, iters_done,
-                             resid, ex_m, ex_trace, ex_score, ex_n);
+                             resid, ex_m, ex_trace, ex_score, ex_n, ex_flags, ex_mult);
+}
+extern "C" int mr_windows_batch_exemplars(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                                          const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                                          int method, int32_t top_max, int precision, int32_t* out_podop, double* out_score,
+                                          int32_t* n_out, int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal,
+                                          int32_t* status, int iters, double tol, int check_every, int32_t* iters_done,
+                                          double* resid, int32_t ex_m, int32_t* ex_trace, double* ex_score, int32_t* ex_n) {
+    return mr_windows_batch_exemplars_ex(ctx, n_windows, spans, t0, t1, a3, a3_valid, method, top_max, precision, out_podop,
+                                         out_score, n_out, edges_traversed, n_abnormal, n_normal, status, iters, tol,
+                                         check_every, iters_done, resid, ex_m, ex_trace, ex_score, ex_n, 0u, nullptr);
 }

@@ -246,6 +246,7 @@ struct mr_graph {
     DBuf<double> mult, mw_tp;
     std::vector<int64_t> tile_mult_h;   // per wave tile: the multiplicity its traces stand for
     DBuf<int32_t> krep;              // [T] class representative of each trace (when allocated)
+    bool krep_ok = false;            // krep holds the representatives of this graph's kinds (the structure never changes)
     int64_t kc_kinds = 0;            // kinds of the last kind-compressed ranking (0: none)
     std::unique_ptr<mr_graph> kc;    // the representatives' graph of a kind-compressed ranking, kept for the next call
     // mr_pagerank_presetup: kinds / preference / iteration state already set up for the next call
@@ -333,6 +334,9 @@ struct mr_graph {
     // [T] by position: the trace's code in its table (lo_tr[pinv[p]]), kept only when the call asked
     // for exemplars (mr_windows_batch_exemplars): pinv is scratch of the build
     DBuf<int32_t> tcode;
+    // [T] by position: the trace's exact kind class in its table (lo_kid[pinv[p]]), kept only when the
+    // call asked for one exemplar per kind (MR_EX_DISTINCT_KINDS)
+    DBuf<int32_t> tkid;
     // [T] by position: the length of the run of identical traces (one kind class, adjacent in a
     // wave tile) a position heads, 0 for the run's other positions (k_tr_a's walk merges the run)
     DBuf<uint8_t> trun;
@@ -572,7 +576,8 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
 // four launches; gs[i] built from sps[i / 2] with builds bs[i]
 int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const* sps, IxBuild* const* bs,
                         const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep,
-                        bool keep_tcode = false);   // keep_tcode: one more launch fills mr_graph.tcode
+                        bool keep_tcode = false,    // keep_tcode: one more launch fills mr_graph.tcode
+                        bool keep_tkid = false);    // ... and mr_graph.tkid (with keep_tcode only)
 // a graph of mr_ix_launch / mr_ix_launch2 finished WITHOUT its prepare: the caller prepares many
 // such graphs together (mr_graph_prepare_batch)
 int mr_ix_finish_unprepared(mr_ctx* ctx, const mr_spans* sp, mr_graph* g, IxBuild& b, const int64_t* h);
@@ -584,7 +589,8 @@ int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who);
 // detector's abnormal traces g, the iterations K it ran, n_ops (<= 64, distinct) pod-op codes; its
 // rows go to trace / score [n_ops * m] and cnt [n_ops] (host).  Layout-order graphs (g->lo, tcode
 // kept) share one selection and one merge launch and one pinned read-back; the others go through
-// mr_graph_exemplars a window at a time.
+// mr_graph_exemplars a window at a time.  flags: mr_graph_exemplars_ex's; MR_EX_DISTINCT_KINDS reads
+// tkid beside tcode and fills mult [n_ops * m] (or null), the class size of every entry.
 struct MrWinEx {
     mr_graph* g;
     int32_t K, n_ops;
@@ -593,8 +599,13 @@ struct MrWinEx {
     int32_t* trace;
     double* score;
     int32_t* cnt;
+    int32_t* mult;
 };
-int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m);
+int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m, uint32_t flags);
+// mr_pr_kinds.hip: g->krep, every trace's class representative (the kinds' exact classes), for a
+// graph with a trace-major incidence: computed at the first call, kept with the graph.  Touches
+// nothing a ranking left behind (kind, pref, c_t, the flag and sum words stay as they are).
+int mr_kind_reps_ensure(mr_ctx* ctx, mr_graph* g);
 // mr_pagerank_presetup of n graphs in six launches when all allow the batched set-up (keep: its
 // host descriptors, alive until the stream has used them)
 int mr_pagerank_presetup_n(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int n, double d, int precision,

@@ -490,6 +490,75 @@ int graph_kinds(mr_ctx* ctx, mr_graph* g, bool chk, bool ktab, uint64_t cap, uin
     return MR_OK;
 }
 
+// Kinds with representatives: g->kind and g->krep under the seed sequence of mr_pagerank_batch_impl,
+// a 64-bit key collision rerun with the next seed.  call_reset: the reset of a ranking's set-up
+// (pr_reset_launch over the T traces: pref and c_t cleared too, as the kind-compressed ranking does
+// ahead of its own); else only the words the kinds themselves need (the hash table, flag, scal).
+static int kinds_with_reps(mr_ctx* ctx, mr_graph* g, bool call_reset) {
+    hipStream_t st = ctx->stream;
+    const int32_t T = g->T, N = g->N;
+    uint64_t cap = 1;
+    while (cap < 2ull * (uint64_t)T) cap <<= 1;
+    const bool ktab = (int64_t)T < kind_part_min();
+    if (!ktab) cap = 0;
+    MR_TRY(g->kind.alloc(ctx, (size_t)T));
+    MR_TRY(g->krep.alloc(ctx, (size_t)T));
+    if (call_reset) {
+        MR_TRY(g->pref.alloc(ctx, (size_t)T));
+        MR_TRY(g->c_t.alloc(ctx, (size_t)T));
+    }
+    MR_TRY(g->flag.alloc(ctx, 8));
+    MR_TRY(g->scal.alloc(ctx, 8));
+    if (ktab) {
+        MR_TRY(g->ht_key.alloc(ctx, cap));
+        MR_TRY(g->ht_cr.alloc(ctx, cap));
+        MR_TRY(g->slot_of.alloc(ctx, (size_t)T));
+    }
+    bool ok = false;
+    for (int a = 0; a < 4 && !ok; ++a) {
+        pr_reset_launch(ctx, call_reset ? T : 0, (int64_t)cap, N, g->pref.p, g->c_t.p, g->ht_key.p, g->ht_cr.p, g->flag.p,
+                        g->scal.p);
+        MR_TRY(graph_kinds(ctx, g, false, ktab, cap, kind_seed(a), kind_hmask(a)));
+        int32_t hf[4];
+        MR_TRY(g->flag.download(ctx, hf, 4));
+        MR_TRY_HIP(ctx, hipStreamSynchronize(st));
+        if (hf[2] & 1) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: a partition exceeded its table");
+        ok = !(hf[0] & 1);
+    }
+    if (!ok) return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under 4 seeds");
+    g->krep_ok = true;
+    return MR_OK;
+}
+
+// mr_internal.h: the representatives for the exemplars' one-per-kind selection, after a ranking.  The
+// kinds run on buffers of their own, swapped into the graph for the step: the class sizes a ranking
+// left (kind), its flag and sum words and its hash table are what they were when the step returns,
+// pref and c_t are never touched -- k_trace_rank, mr_graph_fetch and the next ranking read them.
+int mr_kind_reps_ensure(mr_ctx* ctx, mr_graph* g) {
+    if (g->krep_ok && g->krep.p) return MR_OK;
+    const int64_t* koff = g->rs_is_sr ? g->rs_off.p : g->srt_off.p;
+    if (!koff || !g->w_t.p) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: the graph has no trace-major incidence");
+    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    struct Swap {   // the graph's own buffers aside while the kinds run, back on every way out
+        mr_graph* g;
+        DBuf<double> kind, scal;
+        DBuf<int32_t> flag, slot_of;
+        DBuf<unsigned long long> ht_key;
+        DBuf<KCnt> ht_cr;
+        void flip() {
+            g->kind.swap(kind);
+            g->scal.swap(scal);
+            g->flag.swap(flag);
+            g->slot_of.swap(slot_of);
+            g->ht_key.swap(ht_key);
+            g->ht_cr.swap(ht_cr);
+        }
+        explicit Swap(mr_graph* g_) : g(g_) { flip(); }
+        ~Swap() { flip(); }
+    } aside(g);
+    return kinds_with_reps(ctx, g, false);   // (synchronised: its last read-back waited for the stream)
+}
+
 // MR_PR_KIND_COMPRESS (§8(f) f4): kinds of g with each trace's class representative, then a graph
 // of the K representatives (multiplicities carried in q and in the preference sums), ranked
 // by the same fused iteration; its weights are g's.  Graphs off the fused path (or with
@@ -517,33 +586,7 @@ static int kind_compressed_pagerank(mr_ctx* ctx, mr_graph* g, int anomaly, doubl
     };
     if (g->kc && getenv("MR_KC_NOCACHE") == nullptr) return rank_kc(g->kc.get());
     g->kc.reset();
-    // ---- kinds with representatives (the seed sequence of mr_pagerank_batch_impl)
-    uint64_t cap = 1;
-    while (cap < 2ull * (uint64_t)T) cap <<= 1;
-    const bool ktab = (int64_t)T < kind_part_min();
-    if (!ktab) cap = 0;
-    MR_TRY(g->kind.alloc(ctx, (size_t)T));
-    MR_TRY(g->krep.alloc(ctx, (size_t)T));
-    MR_TRY(g->pref.alloc(ctx, (size_t)T));
-    MR_TRY(g->c_t.alloc(ctx, (size_t)T));
-    MR_TRY(g->flag.alloc(ctx, 8));
-    MR_TRY(g->scal.alloc(ctx, 8));
-    if (ktab) {
-        MR_TRY(g->ht_key.alloc(ctx, cap));
-        MR_TRY(g->ht_cr.alloc(ctx, cap));
-        MR_TRY(g->slot_of.alloc(ctx, (size_t)T));
-    }
-    bool ok = false;
-    for (int a = 0; a < 4 && !ok; ++a) {
-        pr_reset_launch(ctx, T, (int64_t)cap, N, g->pref.p, g->c_t.p, g->ht_key.p, g->ht_cr.p, g->flag.p, g->scal.p);
-        MR_TRY(graph_kinds(ctx, g, false, ktab, cap, kind_seed(a), kind_hmask(a)));
-        int32_t hf[4];
-        MR_TRY(g->flag.download(ctx, hf, 4));
-        MR_TRY_HIP(ctx, hipStreamSynchronize(st));
-        if (hf[2] & 1) return mr_fail(ctx, MR_ERR_STATE, "trace kinds: a partition exceeded its table");
-        ok = !(hf[0] & 1);
-    }
-    if (!ok) return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under 4 seeds");
+    MR_TRY(kinds_with_reps(ctx, g, true));
     // ---- the representatives' graph
     DBuf<int32_t> fl, rep, cnt;
     DBuf<int64_t> pos, tmp;

@@ -360,15 +360,22 @@ __global__ void __launch_bounds__(256) k_lo_fill_b(const LDev* __restrict__ ld, 
 }
 // (a call that asked for exemplars only) the trace code of every position, tcode[p] = lo_tr[pinv[p]]:
 // pinv leaves with the build.  One descriptor per graph, the blocks found as k_lo_apply_b's.
+// tkid (a call that asked for one exemplar per kind, else null): tkid[p] = lo_kid[pinv[p]], the
+// table's exact kind class of the trace.
 struct LTDev {
     const int32_t *pinv, *lo_tr;
     int32_t* tcode;
     int32_t T, b0;
+    const int32_t* lo_kid;
+    int32_t* tkid;
 };
 __global__ void __launch_bounds__(256) k_lo_tcode_b(const LTDev* __restrict__ lt, int32_t n) {
     const LTDev& G = lt[block_owner<LTDev, &LTDev::b0>(lt, n, (int32_t)blockIdx.x)];
     const int64_t p = (int64_t)((int32_t)blockIdx.x - G.b0) * 256 + threadIdx.x;
-    if (p < G.T) G.tcode[p] = G.lo_tr[G.pinv[p]];
+    if (p >= G.T) return;
+    const int32_t ix = G.pinv[p];
+    G.tcode[p] = G.lo_tr[ix];
+    if (G.tkid) G.tkid[p] = G.lo_kid[ix];
 }
 __global__ void __launch_bounds__(1024) k_lo_total_b(const LDev* __restrict__ ld) {   // block g: graph g
     const LDev& G = ld[blockIdx.x];
@@ -507,7 +514,7 @@ static int lo_setup_one(mr_ctx* ctx, mr_graph* g, int anomaly, double d, bool fp
 
 int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const* sps, IxBuild* const* bs,
                         const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep,
-                        bool keep_tcode) {
+                        bool keep_tcode, bool keep_tkid) {
     if (n <= 0) return MR_OK;
     const bool fp32 = precision == MR_FP32;
     hipStream_t st = ctx->stream;
@@ -609,7 +616,9 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
             for (int i = 0; i < n; ++i) {
                 if (anomaly[i] != 0) continue;
                 MR_TRY(gs[i]->tcode.alloc(ctx, (size_t)gs[i]->T));
-                lt.push_back(LTDev{bs[i]->pinv.p, sps[i]->lo_tr.p, gs[i]->tcode.p, gs[i]->T, b0});
+                if (keep_tkid) MR_TRY(gs[i]->tkid.alloc(ctx, (size_t)gs[i]->T));
+                lt.push_back(LTDev{bs[i]->pinv.p, sps[i]->lo_tr.p, gs[i]->tcode.p, gs[i]->T, b0, sps[i]->lo_kid.p,
+                                   keep_tkid ? gs[i]->tkid.p : nullptr});
                 b0 += cdiv(gs[i]->T, 256);
             }
             memcpy(keep.data() + k0, lt.data(), lt.size() * sizeof(LTDev));

@@ -143,6 +143,16 @@ def check_exemplar_m(m) -> int:
     return int(m)
 
 
+def check_exemplar_kinds(exemplar_kinds, exemplars) -> bool:
+    """The exemplar_kinds keyword (one exemplar per trace kind) of the entries whose exemplars are
+    optional: it needs exemplars=; raised as ValueError before any library call."""
+    if not isinstance(exemplar_kinds, (bool, np.bool_)):
+        raise ValueError(f"exemplar_kinds must be a bool, not {exemplar_kinds!r}")
+    if exemplar_kinds and exemplars is None:
+        raise ValueError("exemplar_kinds=True needs exemplars=m")
+    return bool(exemplar_kinds)
+
+
 def check_exemplar_ops(ops) -> list:
     """The ops of an exemplar request as a non-empty list (a lone name or index is not a list of them)."""
     if isinstance(ops, (str, bytes)) or not hasattr(ops, "__iter__"):
@@ -273,34 +283,52 @@ class DeviceGraph:
                 raise ValueError(f"unknown op {op!r}") from None
         return out
 
-    def exemplars_raw(self, idx, m: int):
+    def exemplars_raw(self, idx, m: int, distinct_kinds: bool = False):
         """mr_graph_exemplars for node indices (any number: calls of EX_MAX_OPS): (traces [n, m] int32,
-        -1 padded; scores [n, m]; counts [n])."""
+        -1 padded; scores [n, m]; counts [n]).  distinct_kinds (mr_graph_exemplars_ex with
+        MR_EX_DISTINCT_KINDS): one trace per trace kind, and a 4th array, the kinds' class sizes
+        [n, m] int32, 0 padded."""
         lib = _lib.load()
         n = len(idx)
         tr = np.empty((n, m), np.int32)
         sc = np.empty((n, m), np.float64)
         cnt = np.empty(n, np.int32)
+        mult = np.empty((n, m), np.int32) if distinct_kinds else None
         for b in range(0, n, EX_MAX_OPS):
             ops = np.asarray(idx[b:b + EX_MAX_OPS], np.int32)
             k = int(ops.size)
             t, s, c = np.empty((k, m), np.int32), np.empty((k, m), np.float64), np.empty(k, np.int32)
-            self.ctx.check(lib.mr_graph_exemplars(self.h, ptr(ops, C.c_int32), k, m, ptr(t, C.c_int32),
-                                                  ptr(s, C.c_double), ptr(c, C.c_int32)), "mr_graph_exemplars")
+            if distinct_kinds:
+                mu = np.empty((k, m), np.int32)
+                self.ctx.check(lib.mr_graph_exemplars_ex(self.h, ptr(ops, C.c_int32), k, m, _lib.MR_EX_DISTINCT_KINDS,
+                                                         ptr(t, C.c_int32), ptr(s, C.c_double), ptr(c, C.c_int32),
+                                                         ptr(mu, C.c_int32)), "mr_graph_exemplars_ex")
+                mult[b:b + k] = mu
+            else:
+                self.ctx.check(lib.mr_graph_exemplars(self.h, ptr(ops, C.c_int32), k, m, ptr(t, C.c_int32),
+                                                      ptr(s, C.c_double), ptr(c, C.c_int32)), "mr_graph_exemplars")
             tr[b:b + k], sc[b:b + k], cnt[b:b + k] = t, s, c
-        return tr, sc, cnt
+        return (tr, sc, cnt, mult) if distinct_kinds else (tr, sc, cnt)
 
-    def exemplars(self, ops, m: int = 5) -> dict:
+    def exemplars(self, ops, m: int = 5, distinct_kinds: bool = False) -> dict:
         """For each op (node names or indices) the m traces that matter most to the last ranking among
         the traces the op occurs in (its operation_trace row): {op: [(trace, score), ...]} in request
         order, score descending, ties by trace order; trace is the trace's name (its index on a graph
-        without names), score its entry of trace_rank()."""
+        without names), score its entry of trace_rank().  distinct_kinds: one trace per trace kind
+        (traces with the same operations and span count: the ranking's own classes), each kind by its
+        best trace, as (trace, score, count) with count the number of traces of that kind in the graph."""
         m = check_exemplar_m(m)
         ops = check_exemplar_ops(ops)
         idx = self._node_indices(ops)
-        tr, sc, cnt = self.exemplars_raw(idx, m)
         names = self.traces
         out = {}
+        if distinct_kinds:
+            tr, sc, cnt, mult = self.exemplars_raw(idx, m, True)
+            for i, op in enumerate(ops):
+                out[op] = [(names[int(t)] if names is not None else int(t), np.float64(s), int(c))
+                           for t, s, c in zip(tr[i, :cnt[i]], sc[i, :cnt[i]], mult[i, :cnt[i]])]
+            return out
+        tr, sc, cnt = self.exemplars_raw(idx, m)
         for i, op in enumerate(ops):
             out[op] = [(names[int(t)] if names is not None else int(t), np.float64(s))
                        for t, s in zip(tr[i, :cnt[i]], sc[i, :cnt[i]])]

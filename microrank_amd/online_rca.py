@@ -21,7 +21,7 @@ import pandas as pd
 from . import _lib
 from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
-from .graph import check_converge_args, check_exemplar_m, check_exemplar_ops
+from .graph import check_converge_args, check_exemplar_kinds, check_exemplar_m, check_exemplar_ops
 from .pagerank import ITERATIONS, trace_pagerank
 from .preprocess_data import (PagerankGraph, SpanStream, get_operation_duration_data, get_operation_slo, get_pagerank_graph,  # noqa: F401
                               get_service_operation_list, get_span, span_table)
@@ -107,16 +107,17 @@ def _write_result(top_list, score_list):
             w.writerow(["span", service, rank, float(score)])
 
 
-def _write_exemplars(top_list, score_list, rows):
+def _write_exemplars(top_list, score_list, rows, kinds=False):
     """exemplars.csv beside result.csv: for each op of result.csv, in its order, the traces to open
-    (rows: {op: [(trace, score), ...]}, best first)."""
+    (rows: {op: [(trace, score), ...]}, best first).  kinds: the rows hold (trace, score, count), one
+    trace per trace kind, and the file a 5th column ``traces``: the traces of that kind in the window."""
     ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
     with open("exemplars.csv", "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["result", "rank", "trace", "score"])
+        w.writerow(["result", "rank", "trace", "score"] + (["traces"] if kinds else []))
         for service, _ in ranked:
-            for rank, (trace, score) in enumerate(rows.get(service, []), start=1):
-                w.writerow([service, rank, trace, float(score)])
+            for rank, row in enumerate(rows.get(service, []), start=1):
+                w.writerow([service, rank, row[0], float(row[1])] + ([int(row[2])] if kinds else []))
 
 
 def sweep_plan(ctx, table, dev, a3, ok, t_begin: int, t_end: int, step_normal: int, step_abnormal: int):
@@ -156,16 +157,18 @@ def sweep_chain(plan):
     return events
 
 
-def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None):
+def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
-    exemplars: rank_windows' keyword (a 7th element per window)."""
+    exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window)."""
+    exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
     width = plan["step_n"] * plan["grain"]
     if not todo:
         return {}
     wins = [(plan["dev"], plan["t_begin"] + mm * plan["grain"], plan["t_begin"] + mm * plan["grain"] + width,
              plan["a3"], plan["ok"]) for mm in todo]
-    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=exemplars)))
+    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=exemplars,
+                                       exemplar_kinds=exemplar_kinds)))
 
 
 def _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx):
@@ -189,15 +192,16 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
                       int(window_normal.value), int(window_abnormal.value))
 
 
-def _sweep_run(plan, iters=ITERATIONS, exemplars=None):
+def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
-    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars))
+    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds),
+                exemplar_kinds)
 
 
-def _sweep_emit(plan, events, results):
+def _sweep_emit(plan, events, results, exemplar_kinds=False):
     names = plan["table"].podop_names
     for e in events:
         if e[0] == "empty":
@@ -225,12 +229,14 @@ def _sweep_emit(plan, events, results):
         _write_result(top_list, score_list)
         if len(results[mm]) > 6:   # (exemplars asked: the batch's answer, trace names where the table has them)
             tnames = plan["table"].trace_names
-            rows = {(names[c] if names is not None else c): [(tnames[t] if tnames is not None else t, v) for t, v in lst]
+            rows = {(names[c] if names is not None else c): [(tnames[r[0]] if tnames is not None else r[0],) + tuple(r[1:])
+                                                             for r in lst]
                     for c, lst in results[mm][6].items()}
-            _write_exemplars(top_list, score_list, rows)
+            _write_exemplars(top_list, score_list, rows, exemplar_kinds)
 
 
-def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None):
+def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
+                              exemplar_kinds=False):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -245,8 +251,13 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     exemplars: an integer m (1..32): every trigger also rewrites ``exemplars.csv`` beside result.csv
     (columns result, rank, trace, score): for each op of result.csv the m abnormal traces of the
     window to open first.  On the sweep path from the batch's own answer (rank_windows), window by
-    window from window_exemplars.  stdout and result.csv do not change; without it no file is written."""
+    window from window_exemplars.  stdout and result.csv do not change; without it no file is written.
+
+    exemplar_kinds (with exemplars): one trace per trace kind (traces of the window with the same
+    pod-ops and span count), each kind by its best trace; exemplars.csv gains a 5th column ``traces``,
+    the number of abnormal traces of the window of that kind.  Without it the file is unchanged."""
     check_converge_args(0.0, iters, 1)
+    exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
     window_normal = pd.Timedelta(minutes=5)
@@ -255,11 +266,11 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters, exemplars)
-    _window_loop(data, slo, operation_list, start, end, iters, exemplars)
+        return _sweep_run(plan, iters, exemplars, exemplar_kinds)
+    _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds)
 
 
-def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None):
+def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -287,8 +298,9 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
             print(top_list, score_list)
             _write_result(top_list, score_list)
             if exemplars is not None:
-                rows = window_exemplars(data, start_time, end_time, slo, top_list, m=exemplars, iters=iters) if top_list else {}
-                _write_exemplars(top_list, score_list, rows)
+                rows = window_exemplars(data, start_time, end_time, slo, top_list, m=exemplars, iters=iters,
+                                        distinct_kinds=exemplar_kinds) if top_list else {}
+                _write_exemplars(top_list, score_list, rows, exemplar_kinds)
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -304,14 +316,16 @@ class RCAStream:
     concatenated chunks.  Spans of traces that start before the chain's next window are dropped,
     so the resident table stays a few windows long; each push re-ingests that table on the device
     (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
-    iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars: its
-    keyword (exemplars.csv rewritten at every trigger)."""
+    iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars,
+    exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
-    def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None):
+    def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
+                 exemplar_kinds=False):
         check_converge_args(0.0, iters, 1)
+        self.exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
         self.exemplars = None if exemplars is None else check_exemplar_m(exemplars)
         self.slo, self.operation_list, self.iters = slo, operation_list, iters
         self.ctx = ctx or _lib.default_context()
@@ -380,12 +394,14 @@ class RCAStream:
             if plan is None:   # window times vary within a trace: window by window
                 data = self._frame()
                 if final:
-                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars)
+                    self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
+                                            self.exemplar_kinds)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
                 events = sweep_chain(plan)
-                _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars))
+                _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars,
+                                                     exemplar_kinds=self.exemplar_kinds), self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -402,7 +418,7 @@ class RCAStream:
         cur = self.cur
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
-                               self.exemplars)
+                               self.exemplars, self.exemplar_kinds)
             cur = nxt
         return cur
 
@@ -422,16 +438,18 @@ def _window_report(iters_done, resid, i):
 
 
 def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATIONS, precision="fp64", ctx=None,
-                     table=None, dev=None):
+                     table=None, dev=None, distinct_kinds=False):
     """The traces to open for the ops a window's ranking names: for each pod-op of ``ops`` (names, or
     pod-op codes) the m abnormal traces of the window that matter most to the ranking among those the
     op occurs in -- {pod-op: [(traceID, score), ...]}, score descending.  Composed from entries that
     exist: mr_detect -> the abnormal traces' mask -> mr_graph_build -> mr_pagerank_ex (anomaly = 0:
     the flag the window path gives the graph of the detector's abnormal traces, T1) ->
     mr_graph_exemplars (DeviceGraph.exemplars).  An op absent from that graph maps to []; an empty
-    window, or one without abnormal traces, returns {}."""
+    window, or one without abnormal traces, returns {}.  distinct_kinds: one trace per trace kind of
+    that graph (DeviceGraph.exemplars' keyword): (traceID, score, traces of that kind)."""
     m = check_exemplar_m(m)
     ops = check_exemplar_ops(ops)
+    distinct_kinds = check_exemplar_kinds(distinct_kinds, m)
     if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
         raise ValueError(f"iters must be an integer >= 0, not {iters!r}")
     ctx = ctx or _lib.default_context()
@@ -462,7 +480,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
         have = [i for i in idx if i >= 0]
         out = {op: [] for op in ops}
         if have:
-            tr, sc, cnt = g.exemplars_raw(have, m)
+            tr, sc, cnt, *mult = g.exemplars_raw(have, m, distinct_kinds)
             tnames = table.trace_names
             j = 0
             for op, i in zip(ops, idx):
@@ -470,6 +488,8 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
                     continue
                 out[op] = [(tnames[int(pg.trace_code[t])] if tnames is not None else int(pg.trace_code[t]), np.float64(s))
                            for t, s in zip(tr[j, :cnt[j]], sc[j, :cnt[j]])]
+                if distinct_kinds:
+                    out[op] = [r + (int(c),) for r, c in zip(out[op], mult[0][j, :cnt[j]])]
                 j += 1
         return out
     finally:
@@ -477,7 +497,8 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 
 
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
-               table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None):
+               table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
+               exemplar_kinds=False):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -489,8 +510,10 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
 
     exemplars: an integer m adds the key ``"exemplars"``: window_exemplars for the ops of the top
     list, with this call's iters (with tol, the iterations the report says were run).  Every other
-    key is what the call returns without the keyword."""
+    key is what the call returns without the keyword.  exemplar_kinds (with exemplars): window_exemplars'
+    distinct_kinds -- one trace per trace kind, as (traceID, score, traces of that kind)."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
     ctx = ctx or _lib.default_context()
@@ -520,26 +543,32 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     if exemplars is not None:
         k_run = int(iters_done[0]) if tol > 0.0 else int(iters)
         res["exemplars"] = window_exemplars(data, start_time, end_time, slo, res["top"], m=exemplars, iters=k_run,
-                                            precision=precision, ctx=ctx, table=table, dev=dev) if m else {}
+                                            precision=precision, ctx=ctx, table=table, dev=dev,
+                                            distinct_kinds=exemplar_kinds) if m else {}
     return res
 
 
-def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c):
+def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):
     """mr_windows_batch_exemplars' arrays as one {pod-op code: [(trace code, np.float64 score), ...]}
-    per window (whole-array conversions: a Python-level loop per score costs more than the device side)."""
+    per window (whole-array conversions: a Python-level loop per score costs more than the device side).
+    ex_m (mr_windows_batch_exemplars_ex's class sizes): triples (trace code, score, class size)."""
     cod, cnt, no, tl, sl = codes.tolist(), ex_c.tolist(), n_out.tolist(), ex_t.tolist(), list(ex_s)
+    ml = ex_m.tolist() if ex_m is not None else None
     out = []
     for i in range(n):
         rows = {}
         for j in range(i * k, i * k + no[i]):
             b = j * m
+            if ml is not None:
+                rows[cod[j]] = list(zip(tl[b:b + cnt[j]], sl[b:b + cnt[j]], ml[b:b + cnt[j]]))
+                continue
             rows[cod[j]] = list(zip(tl[b:b + cnt[j]], sl[b:b + cnt[j]]))
         out.append(rows)
     return out
 
 
 def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision="fp64", iters=ITERATIONS, tol=None,
-                 check_every=5, info=None, exemplars=None):
+                 check_every=5, info=None, exemplars=None, exemplar_kinds=False):
     """C3: many RCA windows in one call (mr_windows_batch_ex).  ``windows``: a list of
     (DeviceSpans, t0_ns, t1_ns, a3, a3_valid) (the SLO arrays over the table's service-op
     codes).  Returns per window (top pod-op codes, scores, n_abnormal, n_normal, edges, status);
@@ -555,8 +584,13 @@ def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision
     np.float64 score), ...]} for the codes of its top list, in top-list order -- for each the m
     abnormal traces of the window that matter most to the ranking among those the pod-op occurs in,
     score descending; [] for a pod-op that occurs only in the window's normal traces.  Without the
-    keyword the tuples stay 6 long, through mr_windows_batch_ex."""
+    keyword the tuples stay 6 long, through mr_windows_batch_ex.
+
+    exemplar_kinds (with exemplars; mr_windows_batch_exemplars_ex, MR_EX_DISTINCT_KINDS): one trace per
+    trace kind of the window's graph of abnormal traces, each kind by its best trace, and the 7th
+    element holds triples (trace code, score, traces of that kind in that graph)."""
     tol = _iter_args(iters, tol, check_every, info, list)
+    exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
     n = len(windows)
@@ -586,12 +620,18 @@ def rank_windows(ctx, windows, *, top_max=5, spectrum_method="dstar2", precision
         ex_t = np.full(max(n, 1) * k * m, -1, np.int32)
         ex_s = np.zeros(max(n, 1) * k * m, np.float64)
         ex_c = np.zeros(max(n, 1) * k, np.int32)
-        ctx.check(_lib.load().mr_windows_batch_exemplars(*args, m, ptr(ex_t, C.c_int32), ptr(ex_s, C.c_double),
-                                                         ptr(ex_c, C.c_int32)), "mr_windows_batch_exemplars")
+        ex_mu = np.zeros(max(n, 1) * k * m, np.int32) if exemplar_kinds else None
+        if exemplar_kinds:
+            ctx.check(_lib.load().mr_windows_batch_exemplars_ex(*args, m, ptr(ex_t, C.c_int32), ptr(ex_s, C.c_double),
+                                                                ptr(ex_c, C.c_int32), _lib.MR_EX_DISTINCT_KINDS,
+                                                                ptr(ex_mu, C.c_int32)), "mr_windows_batch_exemplars_ex")
+        else:
+            ctx.check(_lib.load().mr_windows_batch_exemplars(*args, m, ptr(ex_t, C.c_int32), ptr(ex_s, C.c_double),
+                                                             ptr(ex_c, C.c_int32)), "mr_windows_batch_exemplars")
     if want:
         info.extend(_window_report(iters_done, resid, i) for i in range(n))
     out = [(codes[i * k:i * k + n_out[i]].copy(), scores[i * k:i * k + n_out[i]].copy(), int(na[i]), int(nn[i]),
             int(edges[i]), int(status[i])) for i in range(n)]
     if exemplars is None:
         return out
-    return [res + (rows,) for res, rows in zip(out, _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c))]
+    return [res + (rows,) for res, rows in zip(out, _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_mu))]
