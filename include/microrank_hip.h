@@ -467,6 +467,62 @@ int mr_rca_window_ex(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, con
                      int32_t* n_abnormal, int32_t* n_normal, int iters, double tol, int check_every,
                      int32_t* iters_done, double* resid);
 
+/* ------------------------------------------------------------------ latency evidence
+ * How slow is a suspect op in the abnormal traces, compared with the normal traces of the same
+ * window?  No reference counterpart: the evidence an operator holds against a ranking before
+ * believing it.  Per row i of a span table the value is
+ *   MR_LAT_DURATION  duration[i]
+ *   MR_LAT_SELF      duration[i] - csum[span[i]], csum[c] the sum of duration[j] over ALL rows j of
+ *                    the table with parent[j] == c (parent[j] < 0 adds nothing); int64 arithmetic
+ *                    that wraps, as numpy's.  The join is T11's: it ignores traceID, rows that
+ *                    share a spanID code each receive the full child sum, an orphan's parent code
+ *                    is -1.  Self time may be negative (duplicated spanIDs, broken traces).  csum
+ *                    depends on the table alone: it is computed by the first call that needs it
+ *                    and kept with the table, in a buffer nothing else reads.
+ * A span's duration contains its children's, so every ancestor of a slow op looks slow; its self
+ * time does not.
+ * The selected rows of pod-op p, side s (0 normal, 1 abnormal, in the DETECTOR's sense -- the sense
+ * the exemplars use) are the rows with podop[i] == p, state[trace[i]] == s + 1 (mr_detect's
+ * state: 0 outside the window or dropped, 1 normal, 2 abnormal) and tstart[i] >= t0 && tend[i] <= t1
+ * (inclusive; t0 == INT64_MIN and t1 == INT64_MAX: the whole table, as in mr_slo_quantiles).
+ * Per asked op and side: count, the number of selected rows, and for each q[j]
+ * numpy.quantile(values, q[j], method=...) with mr_slo_quantiles' three methods, bit for bit, in
+ * duration units, not scaled and not rounded; a count of 0 gives 0.0.
+ *
+ * mr_op_latency: one window, the partition given by the caller (mr_detect's state[], host).
+ * out[(j * 2 + side) * n_q + k] answers podops[j] and q[k]; count[j * 2 + side].  A duplicated
+ * asked op is answered each time.
+ * MR_ERR_ARG: a null pointer, n_ops outside 1..64 (mr_graph_exemplars' op limit), n_q outside
+ * 1..16, an unknown what or method, a q[j] that is NaN or outside [0, 1], an asked op outside
+ * [0, n_podops), s of another context, or a value range too wide to sort: grouping and ordering
+ * are ONE sort of keys class << DB | (value - min) over the selected rows, class = (window * K +
+ * slot) * 2 + side, DB = bits of (max - min) of the selected values, and bits(n_windows * K * 2) +
+ * DB must not exceed 64.  MR_ERR_STATE: a time window on a table without trace-level times;
+ * MR_LAT_SELF on a shard of a larger table (cols.row set: children may lie on another rank).
+ * An argument error leaves the context usable. */
+enum { MR_LAT_DURATION = 0, MR_LAT_SELF = 1 };
+int mr_op_latency(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1,
+                  const uint8_t* state /*[n_traces] host*/, const int32_t* podops, int32_t n_ops, int what,
+                  const double* q, int32_t n_q, int method, double* out /*[n_ops * 2 * n_q]: op, side, q */,
+                  int64_t* count /*[n_ops * 2]*/);
+
+/* Many windows: window i = spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i] as in mr_windows_batch; the
+ * partition is that window's mr_detect partition, computed on the device and never copied out.
+ * podops[i * K + j], j < n_ops[i], are the asked ops: the row a ranking call returned in out_podop
+ * with its n_out, K = that call's top_max + 6.  Entries j >= n_ops[i] are ignored: their out / count
+ * are 0.  out[((i * K + j) * 2 + side) * n_q + k], count[(i * K + j) * 2 + side].  status[i]: MR_OK,
+ * or MR_ERR_VALUE for an empty window (T2), whose out / count are 0.  One sort, one bounds pass and
+ * one pick launch answer the whole call; a window's answer does not depend on its place in the call
+ * or on the other windows.  The ranking entries (mr_windows_batch*, mr_rca_window*) are untouched:
+ * evidence is a separate call that takes their top lists.
+ * MR_ERR_ARG: K outside 1..64, n_ops[i] outside 0..K, and everything mr_op_latency rejects.
+ * MR_ERR_STATE: a table without trace-level times; MR_LAT_SELF on a shard. */
+int mr_windows_latency(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                       const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                       const int32_t* podops, const int32_t* n_ops, int32_t K, int what, const double* q,
+                       int32_t n_q, int method, double* out /*[n_windows * K * 2 * n_q]*/,
+                       int64_t* count /*[n_windows * K * 2]*/, int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

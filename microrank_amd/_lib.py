@@ -23,6 +23,8 @@ MR_PR_KIND_COMPRESS = 2   # mr_pagerank: iterate over one representative per tra
 MR_Q_LINEAR, MR_Q_LOWER, MR_Q_HIGHER = 0, 1, 2   # mr_slo_quantiles: numpy.quantile's method= names
 QUANTILE_METHODS = {"linear": MR_Q_LINEAR, "lower": MR_Q_LOWER, "higher": MR_Q_HIGHER}
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1   # mr_slo_quantiles: t0 / t1 of "the whole table"
+MR_LAT_DURATION, MR_LAT_SELF = 0, 1   # mr_op_latency / mr_windows_latency: the value of a row
+LATENCY_VALUES = {"duration": MR_LAT_DURATION, "self": MR_LAT_SELF}
 
 SPECTRUM_METHODS = ("dstar2", "ochiai", "jaccard", "sorensendice", "m1", "m2", "goodman", "tarantula",
                     "russellrao", "hamann", "dice", "simplematcing", "rogers")
@@ -127,6 +129,12 @@ SIGNATURES = {
                                                 C.c_int32, i32p, f64p, i32p, C.c_uint32, i32p]),
     "mr_rca_window_ex": (C.c_int, [P, P, C.c_int64, C.c_int64, f64p, u8p, C.c_int, C.c_int32, C.c_int,
                                    i32p, f64p, i32p, i64p, i32p, i32p, C.c_int, C.c_double, C.c_int, i32p, f64p]),
+    # latency evidence: one window with the caller's partition; many windows with their detectors'
+    "mr_op_latency": (C.c_int, [P, P, C.c_int64, C.c_int64, u8p, i32p, C.c_int32, C.c_int, f64p, C.c_int32, C.c_int,
+                                f64p, i64p]),
+    "mr_windows_latency": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, f64p, C.c_int32, C.c_int,
+                                     f64p, i64p, i32p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "mr_comm_init": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),

@@ -162,7 +162,8 @@ __global__ void k_union_n(const int32_t* n_podop, int32_t Nn, const double* n_w,
 }  // namespace
 
 // Detector on the device; d_state[n_traces] receives 0/1/2.  Returns MR_ERR_VALUE for an empty window.
-static int detect_dev(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* d_a3, const uint8_t* d_a3v,
+// (mr_internal.h: mr_windows_latency runs its windows' detectors through it)
+int mr_detect_dev(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* d_a3, const uint8_t* d_a3v,
                       uint8_t* d_state, int32_t* n_abn, int32_t* n_nor, int64_t* n_in) {
     hipStream_t st = ctx->stream;
     const int64_t S = s->S;
@@ -234,7 +235,7 @@ extern "C" int mr_detect(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1,
     MR_TRY(dv.upload(ctx, a3_valid, s->n_svcops));
     MR_TRY(dst.zero(ctx, s->n_traces));
     *n_abnormal = *n_normal = 0;
-    MR_TRY(detect_dev(ctx, s, t0, t1, da3.p, dv.p, dst.p, n_abnormal, n_normal, n_spans_in_window));
+    MR_TRY(mr_detect_dev(ctx, s, t0, t1, da3.p, dv.p, dst.p, n_abnormal, n_normal, n_spans_in_window));
     MR_TRY(dst.download(ctx, state, s->n_traces));
     MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MR_OK;
@@ -334,7 +335,7 @@ static int win_detect_build(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t 
     MR_TRY(da3.upload(ctx, a3, s->n_svcops));
     MR_TRY(dv.upload(ctx, a3_valid, s->n_svcops));
     MR_TRY(dst.zero(ctx, NT));
-    MR_TRY(detect_dev(ctx, s, t0, t1, da3.p, dv.p, dst.p, &w.na, &w.nn, &w.nin));
+    MR_TRY(mr_detect_dev(ctx, s, t0, t1, da3.p, dv.p, dst.p, &w.na, &w.nn, &w.nin));
     if (mk) mk->mark("detect");
     // T1: the driver unpacks (flag, normal_list, abnormal_list) from (flag, abnormal, normal)
     if (w.na == 0 || w.nn == 0) return MR_OK;   // no anomaly, or one list empty: nothing is ranked

@@ -417,6 +417,11 @@ struct mr_spans {
     DBuf<uint8_t> raw_bytes[6], raw_valid;
     DBuf<int64_t> src;
     int64_t src_next = 0;
+    // latency evidence (mr_latency.hip): csum[c] = sum of duration over the rows whose parent is
+    // span code c ([n_span_codes], int64 sums that wrap), computed by the first MR_LAT_SELF call
+    // on this table and kept: the table is immutable.  Nothing else reads or writes it.
+    mutable DBuf<unsigned long long> csum;
+    mutable bool csum_ok = false;
 };
 
 int mr_spans_index(mr_ctx* ctx, mr_spans* s);
@@ -531,6 +536,11 @@ int mr_pagerank_batch_report(mr_ctx* ctx, mr_graph* const* gs, const int* anomal
 int mr_ix_launch2_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, uint8_t* const* d_states, mr_graph* const* g0s,
                         mr_graph* const* g1s, IxBuild* const* b0s, IxBuild* const* b1s, int64_t* const* d_outs,
                         const DetIn* dets, bool fuse);
+// the window detector on the device (mr_detect.hip; mr_detect without its uploads and its state
+// download): d_state[n_traces], zeroed by the caller, receives 0 / 1 / 2; the counts come back on
+// the host (one stream synchronise).  MR_ERR_VALUE with *n_in = 0 for an empty window.
+int mr_detect_dev(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* d_a3, const uint8_t* d_a3v,
+                  uint8_t* d_state, int32_t* n_abn, int32_t* n_nor, int64_t* n_in);
 constexpr int MR_DETECT_SHARDS = 64;
 int mr_detect_indexed_launch(mr_ctx* ctx, const mr_spans* s, int64_t t0, int64_t t1, const double* d_a3,
                              const uint8_t* d_a3v, uint8_t* d_state, unsigned long long* counts);

@@ -10,7 +10,8 @@
 //   mr_radix_sort on the low OB + DB bits (no value payload)
 //   k_q_bounds  [start, end) of each op in the sorted keys (as k_slo_count does)
 //   k_q_pick    one thread per (op, quantile): numpy 2.x's _quantile arithmetic on the one or two
-//               order statistics it needs, restored from the keys
+//               order statistics it needs, restored from the keys (mr_quantile_dev.h, shared with
+//               mr_latency.hip)
 // DB = bits of (dmax - dmin), OB = bits of n_svcops; OB + DB > 64 is MR_ERR_ARG.
 #include <algorithm>
 #include <climits>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "mr_prim.h"
+#include "mr_quantile_dev.h"
 #include "mr_sort.h"
 
 namespace {
@@ -76,53 +78,13 @@ __global__ void k_q_keys(const int32_t* svcop, const int64_t* dur, const int64_t
 
 // off / endp hold n_ops + 1 slots (the last one is the sentinel's), zeroed by the caller
 __global__ void k_q_bounds(const uint64_t* key, int64_t S, int db, int64_t* off, int64_t* endp) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S) return;
-    const uint64_t k = key[i] >> db;
-    if (i == 0 || (key[i - 1] >> db) != k) off[k] = i;
-    if (i == S - 1 || (key[i + 1] >> db) != k) endp[k] = i + 1;
+    q_bounds_body(key, S, db, off, endp);
 }
 
-// numpy 2.x _quantile for integer data: vi = (n - 1) * q; lower / higher take a[floor / ceil];
-// linear is _lerp(a[p], a[nx], g) with the int64 difference converted once and the result taken
-// from the upper end when g >= 0.5.  (-ffp-contract=off: no multiply-add fuses here.)
+// one thread per (op, quantile): numpy 2.x's _quantile arithmetic (mr_quantile_dev.h)
 __global__ void k_q_pick(const uint64_t* key, const int64_t* off, const int64_t* endp, int32_t n_ops, const double* q,
                          int32_t n_q, int method, int64_t dmin, int db, double* out, int64_t* count) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)n_ops * n_q) return;
-    const int32_t o = (int32_t)(t / n_q), j = (int32_t)(t % n_q);
-    const int64_t beg = off[o], n = endp[o] - beg;
-    if (j == 0) count[o] = n;
-    if (n <= 0) {
-        out[t] = 0.0;
-        return;
-    }
-    const uint64_t mask = db ? (~0ull >> (64 - db)) : 0ull;
-    const double vi = (double)(n - 1) * q[j];
-    const double fl = floor(vi);
-    int64_t p, nx;
-    if (method == MR_Q_LOWER) {
-        p = nx = (int64_t)fl;
-    } else if (method == MR_Q_HIGHER) {
-        p = nx = (int64_t)ceil(vi);
-    } else {
-        p = (int64_t)fl;
-        nx = p + 1;
-        if (vi >= (double)(n - 1)) p = nx = n - 1;
-    }
-    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);   // (q in [0, 1] keeps both inside; never read past the op)
-    nx = nx < 0 ? 0 : (nx > n - 1 ? n - 1 : nx);
-    const int64_t ap = (int64_t)((key[beg + p] & mask) + (uint64_t)dmin);
-    if (method != MR_Q_LINEAR) {
-        out[t] = (double)ap;
-        return;
-    }
-    const int64_t an = (int64_t)((key[beg + nx] & mask) + (uint64_t)dmin);
-    const double g = vi - fl;
-    const double diff = (double)(an - ap);
-    double r = (double)ap + diff * g;
-    if (g >= 0.5) r = (double)an - diff * (1.0 - g);
-    out[t] = r;
+    q_pick_body(key, off, endp, n_ops, q, n_q, method, dmin, db, out, count);
 }
 }  // namespace
 

@@ -23,8 +23,8 @@ from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
 from .graph import check_converge_args, check_exemplar_kinds, check_exemplar_m, check_exemplar_ops
 from .pagerank import ITERATIONS, trace_pagerank
-from .preprocess_data import (PagerankGraph, SpanStream, get_operation_duration_data, get_operation_slo, get_pagerank_graph,  # noqa: F401
-                              get_service_operation_list, get_span, span_table)
+from .preprocess_data import (PagerankGraph, SpanStream, _quantile_args, get_operation_duration_data, get_operation_slo,  # noqa: F401
+                              get_pagerank_graph, get_service_operation_list, get_span, span_table)
 from .spans import to_ns
 
 
@@ -120,6 +120,40 @@ def _write_exemplars(top_list, score_list, rows, kinds=False):
                 w.writerow([service, rank, row[0], float(row[1])] + ([int(row[2])] if kinds else []))
 
 
+def _write_latency(top_list, score_list, rows, qv):
+    """latency.csv beside result.csv: for each op of result.csv, in its order, the quantiles of the
+    op's span values on the normal and then the abnormal traces of the window, one row per q (rows:
+    op_latency's dict; ``spans`` the rows of the op on that side)."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("latency.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "side", "spans", "q", "value"])
+        for rank, (service, _) in enumerate(ranked, start=1):
+            row = rows.get(service)
+            if row is None:
+                continue
+            for side in ("normal", "abnormal"):
+                for qj, v in zip(qv, row[side]):
+                    w.writerow([service, rank, side, int(row["n_" + side]), float(qj), float(v)])
+
+
+def _latency_args(q, what, method="linear"):
+    """(q as a float64 vector, MR_LAT_* code, MR_Q_* code) of the latency keywords; ValueError for a bad
+    q (get_operation_quantiles' rules, at most 16 values), what or method -- before any device work."""
+    qv, code = _quantile_args(q, method)
+    if qv.size > 16:
+        raise ValueError(f"q holds {qv.size} values; at most 16")
+    w = _lib.LATENCY_VALUES.get(what) if isinstance(what, str) else None
+    if w is None:
+        raise ValueError(f"what must be one of {sorted(_lib.LATENCY_VALUES)}, not {what!r}")
+    return qv, w, code
+
+
+def _latency_ms(v):
+    """Raw duration units -> the SLO's unit and rounding (preprocess_data.py:72-73)."""
+    return [np.float64(x) for x in np.round(np.asarray(v, np.float64) / 1000.0, 4)]
+
+
 def sweep_plan(ctx, table, dev, a3, ok, t_begin: int, t_end: int, step_normal: int, step_abnormal: int):
     """SURVEY 8(f) f3 on a resident span table: the detector counts of every window start the
     driver's chain can reach (online_rca.py:161-216: starts t_begin + m * grain while < t_end,
@@ -157,18 +191,28 @@ def sweep_chain(plan):
     return events
 
 
-def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
+def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
+               latency_what="self"):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
-    exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window)."""
+    exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
+    latency (a q, scalar or sequence): ONE windows_latency call over the triggered windows' top lists;
+    its answer goes to plan["latency"] = (q, {m: windows_latency's dict}) for the replay (latency.csv)."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
+    plan.pop("latency", None)
+    if latency is not None:
+        qv = _latency_args(latency, latency_what)[0]
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
     width = plan["step_n"] * plan["grain"]
     if not todo:
         return {}
     wins = [(plan["dev"], plan["t_begin"] + mm * plan["grain"], plan["t_begin"] + mm * plan["grain"] + width,
              plan["a3"], plan["ok"]) for mm in todo]
-    return dict(zip(todo, rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=exemplars,
-                                       exemplar_kinds=exemplar_kinds)))
+    ranked = rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=exemplars,
+                          exemplar_kinds=exemplar_kinds)
+    if latency is not None:
+        lat = windows_latency(plan["ctx"], wins, [r[0] for r in ranked], q=qv, what=latency_what)
+        plan["latency"] = (qv, dict(zip(todo, lat)))
+    return dict(zip(todo, ranked))
 
 
 def _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx):
@@ -192,13 +236,13 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
                       int(window_normal.value), int(window_abnormal.value))
 
 
-def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
+def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self"):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
-    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds),
-                exemplar_kinds)
+    _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds,
+                                         latency=latency, latency_what=latency_what), exemplar_kinds)
 
 
 def _sweep_emit(plan, events, results, exemplar_kinds=False):
@@ -233,10 +277,16 @@ def _sweep_emit(plan, events, results, exemplar_kinds=False):
                                                              for r in lst]
                     for c, lst in results[mm][6].items()}
             _write_exemplars(top_list, score_list, rows, exemplar_kinds)
+        if "latency" in plan:   # (latency asked: the batch's answer in the SLO's unit, by name)
+            qv, lat = plan["latency"]
+            rows = {(names[c] if names is not None else c): {"normal": _latency_ms(r[0]), "abnormal": _latency_ms(r[1]),
+                                                             "n_normal": r[2], "n_abnormal": r[3]}
+                    for c, r in lat[mm].items()}
+            _write_latency(top_list, score_list, rows, qv)
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
-                              exemplar_kinds=False):
+                              exemplar_kinds=False, latency=None, latency_what="self"):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -255,22 +305,33 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
 
     exemplar_kinds (with exemplars): one trace per trace kind (traces of the window with the same
     pod-ops and span count), each kind by its best trace; exemplars.csv gains a 5th column ``traces``,
-    the number of abnormal traces of the window of that kind.  Without it the file is unchanged."""
+    the number of abnormal traces of the window of that kind.  Without it the file is unchanged.
+
+    latency: a q (a float in [0, 1] or a sequence of them): every trigger also rewrites ``latency.csv``
+    beside result.csv (columns result, rank, side, spans, q, value): for each op of result.csv, in its
+    order, the q-quantiles of the op's spans on the window's normal and then abnormal traces (one row
+    per q; ``spans`` the op's rows on that side; value in the SLO's unit and rounding).  latency_what:
+    "self" (a span's duration minus its children's: what separates a cause from its callers) or
+    "duration".  On the sweep path from ONE windows_latency call over the triggered windows, window by
+    window from op_latency.  stdout and result.csv do not change; without it no file is written."""
     check_converge_args(0.0, iters, 1)
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
+    if latency is not None:
+        _latency_args(latency, latency_what)
     window_normal = pd.Timedelta(minutes=5)
     window_abnormal = pd.Timedelta(minutes=4)
     start = data["startTime"].min()
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters, exemplars, exemplar_kinds)
-    _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds)
+        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what)
+    _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what)
 
 
-def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False):
+def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False,
+                 latency=None, latency_what="self"):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -301,6 +362,9 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
                 rows = window_exemplars(data, start_time, end_time, slo, top_list, m=exemplars, iters=iters,
                                         distinct_kinds=exemplar_kinds) if top_list else {}
                 _write_exemplars(top_list, score_list, rows, exemplar_kinds)
+            if latency is not None:
+                rows = op_latency(data, start_time, end_time, slo, top_list, q=latency, what=latency_what) if top_list else {}
+                _write_latency(top_list, score_list, rows, _latency_args(latency, latency_what)[0])
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -317,14 +381,18 @@ class RCAStream:
     so the resident table stays a few windows long; each push re-ingests that table on the device
     (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars,
-    exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger)."""
+    exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger); latency, latency_what: its
+    keywords (latency.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
-                 exemplar_kinds=False):
+                 exemplar_kinds=False, latency=None, latency_what="self"):
         check_converge_args(0.0, iters, 1)
+        if latency is not None:
+            _latency_args(latency, latency_what)
+        self.latency, self.latency_what = latency, latency_what
         self.exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
         self.exemplars = None if exemplars is None else check_exemplar_m(exemplars)
         self.slo, self.operation_list, self.iters = slo, operation_list, iters
@@ -395,13 +463,14 @@ class RCAStream:
                 data = self._frame()
                 if final:
                     self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
-                                            self.exemplar_kinds)
+                                            self.exemplar_kinds, self.latency, self.latency_what)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
                 events = sweep_chain(plan)
                 _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars,
-                                                     exemplar_kinds=self.exemplar_kinds), self.exemplar_kinds)
+                                                     exemplar_kinds=self.exemplar_kinds, latency=self.latency,
+                                                     latency_what=self.latency_what), self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -418,7 +487,7 @@ class RCAStream:
         cur = self.cur
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
-                               self.exemplars, self.exemplar_kinds)
+                               self.exemplars, self.exemplar_kinds, self.latency, self.latency_what)
             cur = nxt
         return cur
 
@@ -498,7 +567,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
-               exemplar_kinds=False):
+               exemplar_kinds=False, latency=None, latency_what="self"):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -511,8 +580,13 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     exemplars: an integer m adds the key ``"exemplars"``: window_exemplars for the ops of the top
     list, with this call's iters (with tol, the iterations the report says were run).  Every other
     key is what the call returns without the keyword.  exemplar_kinds (with exemplars): window_exemplars'
-    distinct_kinds -- one trace per trace kind, as (traceID, score, traces of that kind)."""
+    distinct_kinds -- one trace per trace kind, as (traceID, score, traces of that kind).
+
+    latency: a q (scalar or sequence) adds the key ``"latency"``: op_latency's dict for the ops of the
+    top list (latency_what: "self" or "duration").  Every other key stays what it is."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if latency is not None:
+        _latency_args(latency, latency_what)
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
@@ -545,7 +619,113 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
         res["exemplars"] = window_exemplars(data, start_time, end_time, slo, res["top"], m=exemplars, iters=k_run,
                                             precision=precision, ctx=ctx, table=table, dev=dev,
                                             distinct_kinds=exemplar_kinds) if m else {}
+    if latency is not None:
+        res["latency"] = op_latency(data, start_time, end_time, slo, res["top"], q=latency, what=latency_what, ctx=ctx,
+                                    table=table, dev=dev) if m else {}
     return res
+
+
+def _op_codes(table, ops):
+    """Pod-op codes of ``ops`` (names of the table's pod-ops, or codes); ValueError for any other."""
+    names = table.podop_names
+    code_of = {n: c for c, n in enumerate(names)} if names is not None else {}
+    codes = []
+    for op in ops:
+        if isinstance(op, (int, np.integer)) and not isinstance(op, bool):
+            code = int(op) if 0 <= int(op) < table.n_podops else None
+        else:
+            code = code_of.get(op)
+        if code is None:
+            raise ValueError(f"{op!r} is no pod-op of the span table")
+        codes.append(code)
+    return codes
+
+
+def op_latency(data, start_time, end_time, slo, ops, *, q=(0.5, 0.99), what="self", method="linear", ctx=None,
+               table=None, dev=None):
+    """How slow are the ops a window's ranking names, in the abnormal traces and in the normal ones?
+    For each pod-op of ``ops`` (names, or pod-op codes) the q-quantiles (np.quantile's semantics,
+    ``method`` 'linear', 'lower' or 'higher') of its spans' values on each side of the detector's
+    partition of the window: {op: {"normal": [...], "abnormal": [...], "n_normal": int, "n_abnormal":
+    int}} (mr_detect, then mr_op_latency; csrc/mr_latency.hip).  ``what``: "self" -- a span's duration
+    minus the durations of its children (the spans whose ParentSpanId is its spanID), which does not
+    grow when a callee is slow -- or "duration".  Values are np.float64, np.round(v / 1000.0, 4): the
+    SLO's unit and rounding, as get_operation_quantiles gives them; a side without a span of the op
+    has n 0 and values 0.0.  An op that is no pod-op of the table raises ValueError; an empty window
+    returns {}."""
+    qv, wcode, mcode = _latency_args(q, what, method)
+    ops = list(ops)
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    codes = _op_codes(table, ops)
+    if not ops:
+        return {}
+    a3, ok = slo_arrays(table, slo)
+    state = np.zeros(table.n_traces, np.uint8)
+    na, nn, nin = C.c_int32(), C.c_int32(), C.c_int64()
+    lib = _lib.load()
+    rc = lib.mr_detect(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(a3, C.c_double), ptr(ok, C.c_uint8),
+                       ptr(state, C.c_uint8), C.byref(na), C.byref(nn), C.byref(nin))
+    if rc == _lib.MR_ERR_VALUE and nin.value == 0:
+        return {}
+    ctx.check(rc, "mr_detect")
+    res = {}
+    for b in range(0, len(ops), 64):   # (mr_op_latency's op limit)
+        cod = np.asarray(codes[b:b + 64], np.int32)
+        out = np.zeros((cod.size, 2, qv.size), np.float64)
+        cnt = np.zeros((cod.size, 2), np.int64)
+        ctx.check(lib.mr_op_latency(ctx.h, dev.h, to_ns(start_time), to_ns(end_time), ptr(state, C.c_uint8),
+                                    ptr(cod, C.c_int32), cod.size, wcode, ptr(qv, C.c_double), qv.size, mcode,
+                                    ptr(out, C.c_double), ptr(cnt, C.c_int64)), "mr_op_latency")
+        for j, op in enumerate(ops[b:b + 64]):
+            res[op] = {"normal": _latency_ms(out[j, 0]), "abnormal": _latency_ms(out[j, 1]),
+                       "n_normal": int(cnt[j, 0]), "n_abnormal": int(cnt[j, 1])}
+    return res
+
+
+def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="linear"):
+    """op_latency's evidence for many windows in one call (mr_windows_latency: one sort for all of
+    them).  ``windows`` as rank_windows'; ``ops`` one array of pod-op codes per window -- the first
+    element of rank_windows' tuples.  Returns per window {code: (normal[n_q], abnormal[n_q], n_normal,
+    n_abnormal)} in raw duration units (rank_windows works in codes; names and rounding are the
+    callers'); each window's partition is its own detector's, computed on the device.  An empty
+    window (rank_windows' status MR_ERR_VALUE) answers zeros."""
+    qv, wcode, mcode = _latency_args(q, what, method)
+    n = len(windows)
+    if len(ops) != n:
+        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
+    if n == 0:
+        return []
+    ops = [np.ascontiguousarray(o, np.int32).reshape(-1) for o in ops]
+    k = max(max(o.size for o in ops), 1)
+    if k > 64:
+        raise ValueError(f"a window asks {k} ops; at most 64")
+    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
+           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
+    # (windows that share their SLO arrays give the library one pointer: one upload)
+    addr = {}
+    for i, w in enumerate(windows):
+        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
+            addr.setdefault(id(src), a.ctypes.data)
+    spans = (_lib.P * n)(*[w[0].h for w in windows])
+    t0 = np.array([int(w[1]) for w in windows], np.int64)
+    t1 = np.array([int(w[2]) for w in windows], np.int64)
+    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
+    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
+    cod = np.zeros((n, k), np.int32)
+    n_ops = np.array([o.size for o in ops], np.int32)
+    for i, o in enumerate(ops):
+        cod[i, :o.size] = o
+    out = np.zeros((n, k, 2, qv.size), np.float64)
+    cnt = np.zeros((n, k, 2), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_latency(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                             ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, wcode, ptr(qv, C.c_double),
+                                             qv.size, mcode, ptr(out, C.c_double), ptr(cnt, C.c_int64),
+                                             ptr(status, C.c_int32)), "mr_windows_latency")
+    return [{int(c): (out[i, j, 0].copy(), out[i, j, 1].copy(), int(cnt[i, j, 0]), int(cnt[i, j, 1]))
+             for j, c in enumerate(ops[i])} for i in range(n)]
 
 
 def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):
