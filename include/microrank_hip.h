@@ -137,7 +137,7 @@ int mr_pagerank_batch(mr_ctx* ctx, mr_graph* const* graphs, const int* anomaly, 
  * MR_ERR_ARG: null pointers (converged_at may be NULL), n_graphs < 1, max_iters < 1,
  * check_every < 1, tol negative or NaN, phi <= 0 -- and the two forms this entry does not cover:
  * MR_PR_KIND_COMPRESS and a graph built by mr_graph_build_sharded (an early stop must be agreed
- * over the ranks; mr_pagerank_sharded takes a count).  Window batches build their graphs inside
+ * over the ranks: mr_pagerank_sharded_converge does; mr_pagerank_sharded takes a count).  Window batches build their graphs inside
  * the call, so they have entries of their own: mr_windows_batch_ex and mr_rca_window_ex take a
  * count, report the last iteration's residual and stop at a tolerance.  Everything else as
  * mr_pagerank_batch: its errors, the kind-hash collision retry (which reruns the attempt and
@@ -167,7 +167,8 @@ int mr_graph_fetch(mr_graph* g, double* weight /*[N] host*/, int32_t* coverage /
  * MR_ERR_ARG: null pointers, n_ops outside 1..64, m outside 1..32, an op outside [0, N).
  * MR_ERR_STATE: no ranking yet (or its state re-set since); the last ranking was asked with
  * MR_PR_KIND_COMPRESS (the trace vector then lives on the representatives' graph); a trace shard
- * (mr_graph_build_sharded / mr_pagerank_sharded: each rank holds only its own traces). */
+ * (mr_graph_build_sharded / mr_pagerank_sharded: each rank holds only its own traces;
+ * mr_graph_trace_rank_sharded and mr_graph_exemplars_sharded answer a shard). */
 int mr_graph_trace_rank(mr_graph* g, double* r /*[T] host*/);
 int mr_graph_exemplars(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m,
                        int32_t* out_trace /*[n_ops*m] trace indices, -1 padded*/,
@@ -191,7 +192,7 @@ int mr_graph_exemplars(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m
  * entry and the next ranking bitwise what they were.
  * MR_ERR_ARG: a flag bit other than MR_EX_DISTINCT_KINDS, out_mult with flags == 0, and everything
  * mr_graph_exemplars rejects.  MR_ERR_STATE: as mr_graph_exemplars (no ranking yet,
- * MR_PR_KIND_COMPRESS, a trace shard). */
+ * MR_PR_KIND_COMPRESS, a trace shard: mr_graph_exemplars_sharded has no distinct-kinds form). */
 enum { MR_EX_DISTINCT_KINDS = 1u };
 int mr_graph_exemplars_ex(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m, uint32_t flags,
                           int32_t* out_trace, double* out_score, int32_t* out_n,
@@ -560,6 +561,67 @@ int mr_comm_peer_active(mr_ctx* ctx, int* active);
  * Requires a collective backend (mr_comm_init or mr_comm_set_host). */
 int mr_pagerank_sharded(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int iters,
                         int precision, uint32_t flags);
+
+/* mr_pagerank_sharded with mr_pagerank_converge's convergence report and early stop: the answer to
+ * README.md:37 ("more iterations in PageRank" on a large system) on the path built for large systems,
+ * where pagerank.py:117's fixed count is least likely to fit.  A shard of mr_graph_build_sharded or
+ * an uploaded one.  Collective: every rank calls it, with the same arguments.
+ * After every iteration each rank records resid[k-1] = max over ops of | s_k - s_{k-1} | of the WHOLE
+ * graph (the vectors are replicated after the iteration's all-reduce).  At every check -- every
+ * check_every iterations, at max_iters, or once at the end when tol == 0 -- the stretch's words meet
+ * in one MAX all-reduce over the context's collective (never the peer regions) and only then are
+ * read, so every rank reads the same words and takes the same decision: one small collective per
+ * check, none per iteration.  Before the first iteration the ranks all-gather their requests
+ * (max_iters, check_every, tol, d, alpha, phi, precision, flags, anomaly): ranks that asked
+ * differently would run different numbers of collectives and hang.
+ * Contract: after a call that ran K = *iters_done iterations, mr_graph_fetch is bitwise that of
+ * mr_pagerank_sharded(..., iters = K, ...) on the same shards and backend; resid is identical on
+ * every rank; mr_graph_trace_rank_sharded / mr_graph_exemplars_sharded follow the K iterations.
+ * A kind-hash collision reruns the attempt on every rank and overwrites the history.
+ * One rank without a backend runs with no collective at all.
+ * MR_ERR_ARG: bad handles, iters_done or resid null (converged_at may be NULL), requests that
+ * differ between the ranks (on EVERY rank, before anything ran), max_iters < 1, check_every < 1,
+ * tol negative or NaN, phi <= 0, MR_PR_KIND_COMPRESS.  MR_ERR_COMM: several ranks and no backend.
+ * MR_ERR_STATE: a kind-hash collision under every seed.  Everything else as mr_pagerank_sharded. */
+int mr_pagerank_sharded_converge(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int max_iters,
+                                 double phi, int precision, uint32_t flags, double tol, int check_every,
+                                 int32_t* iters_done,      /* out: iterations run, the same on every rank */
+                                 double* resid,            /* [max_iters] host; entries >= iters_done are 0.0 */
+                                 int32_t* converged_at);   /* one word: first k (1-based) with resid[k-1] <= tol,
+                                                              -1 if none; may be NULL */
+
+/* The trace half of the last SHARDED ranking (mr_pagerank_sharded, mr_pagerank_sharded_converge: the
+ * iterations it ran), for this rank's traces: mr_graph_trace_rank on a shard.  pagerank.py:119-127's
+ * request_ranking_vector is max-normalised over ALL traces; the whole graph's maximum M_r(K) is on
+ * every rank already (it rides the per-iteration all-reduce), so r[t] = (q / w_t) / M_r(K) needs no
+ * exchange and the ranks' vectors concatenate to the whole graph's.  Not collective.  fp64 in both
+ * precisions; K = 0 gives 1 / (N + T of all ranks); the rule for traces without ops is
+ * mr_graph_trace_rank's.  A shard without traces writes nothing.
+ * gid[t] (may be NULL): the trace's global id -- its trace code on a graph of mr_graph_build_sharded
+ * (the codes are global), else the lower ranks' trace count + t (the position in the ranks'
+ * concatenation; the counts are gathered once per graph).
+ * MR_ERR_ARG: g or r null.  MR_ERR_STATE: no ranking yet (or its state re-set since), or the graph's
+ * last ranking was not a sharded one. */
+int mr_graph_trace_rank_sharded(mr_graph* g, double* r /*[T] host: this rank's traces*/,
+                                int64_t* gid /*[T] host or NULL*/);
+/* mr_graph_exemplars over the WHOLE graph of a sharded ranking.  Collective: every rank calls it with
+ * the same ops and m, and every rank receives the same answer.  For each asked node index ops[i] the
+ * m traces with the largest r among the traces of that op's P_sr row on ANY rank (pagerank.py:42-45,
+ * the relation `coverage` counts), score descending, global id (mr_graph_trace_rank_sharded's gid:
+ * the trace code on a graph of mr_graph_build_sharded) ascending on equal fp64 values.  out_n[i] = min(m, coverage[ops[i]] of the whole graph); the rest of
+ * row i is padded with -1 / 0.0.  A duplicated op is answered each time.
+ * Each rank selects from its own traces with mr_graph_exemplars' kernels; the lists meet in ONE
+ * all-gather of a buffer whose size does not depend on the request (64 x 32 records, 64 counts, a
+ * header), and every rank merges them.  A rank without a trace of an op, or without traces, sends
+ * empty lists and still joins the collective.
+ * MR_ERR_ARG: null pointers, n_ops outside 1..64, m outside 1..32, an op outside [0, N), more than
+ * 256 ranks -- checked per rank before the collective, so every rank must pass them alike -- and, on
+ * EVERY rank after it, requests (ops, m) or rankings (iterations, precision) that differ between the
+ * ranks.  MR_ERR_STATE: as mr_graph_trace_rank_sharded.  Not covered: MR_EX_DISTINCT_KINDS across
+ * shards (kinds are merged over the ranks by hash only) and kind-compressed rankings. */
+int mr_graph_exemplars_sharded(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m,
+                               int64_t* out_trace /*[n_ops*m] global ids, -1 padded*/,
+                               double* out_score /*[n_ops*m], 0.0 padded*/, int32_t* out_n /*[n_ops]*/);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,11 @@ SIGNATURES = {
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),
     "mr_comm_set_host": (C.c_int, [P, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "mr_pagerank_sharded": (C.c_int, [P, P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32]),
+    # mr_pagerank_converge's arguments for one shard (collective), then the shard's evidence entries
+    "mr_pagerank_sharded_converge": (C.c_int, [P, P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int,
+                                               C.c_uint32, C.c_double, C.c_int, i32p, f64p, i32p]),
+    "mr_graph_trace_rank_sharded": (C.c_int, [P, f64p, i64p]),
+    "mr_graph_exemplars_sharded": (C.c_int, [P, i32p, C.c_int32, C.c_int32, i64p, f64p, i32p]),
 }
 
 _lib = None

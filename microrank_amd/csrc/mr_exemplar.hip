@@ -635,13 +635,19 @@ static int ex_num_cus() {
     return ncu;
 }
 
-int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who) {
-    if (g->T_all != 0 || g->shard_built)
-        return mr_fail(ctx, MR_ERR_STATE, "%s: a trace shard holds only its own traces", who);
+// shard: the sharded entries' form -- this rank's traces of a graph whose last ranking was
+// mr_pagerank_sharded(_converge): q holds them, the ring's r half the WHOLE graph's M_r(K)
+// (rmax_take_*), sub[(K-1) & 1] and the s half are replicated, v0 counts every rank's traces
+static int trace_rank_fill(mr_ctx* ctx, mr_graph* g, const char* who, bool shard) {
+    if (!shard && (g->T_all != 0 || g->shard_built))
+        return mr_fail(ctx, MR_ERR_STATE, "%s: a trace shard holds only its own traces (mr_graph_trace_rank_sharded / "
+                       "mr_graph_exemplars_sharded answer it)", who);
     if (!g->rk_ok) return mr_fail(ctx, MR_ERR_STATE, "%s: the graph has no ranking yet", who);
+    if (shard && !g->rk_sharded)
+        return mr_fail(ctx, MR_ERR_STATE, "%s: the graph's last ranking was not mr_pagerank_sharded(_converge)", who);
     if (g->rk_kc)
         return mr_fail(ctx, MR_ERR_STATE, "%s: the last ranking was MR_PR_KIND_COMPRESS (its trace vector is the kinds')", who);
-    if (g->lo || (g->fused && !g->tperm.p))
+    if (g->lo || (g->fused && !g->tperm.p && g->T > 0))
         return mr_fail(ctx, MR_ERR_STATE, "%s: a layout-order window graph has no trace-major incidence", who);
     if (g->trank_ok) return MR_OK;
     MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
@@ -649,18 +655,21 @@ int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who) {
     MR_TRY(g->trank.alloc(ctx, (size_t)T));
     const double* q64 = g->rk_fp32 ? nullptr : g->q64[K & 1].p;
     const float* q32 = g->rk_fp32 ? g->q32[K & 1].p : nullptr;
-    if (K > 0 && !(g->rk_fp32 ? (const void*)q32 : (const void*)q64))
+    if (K > 0 && T > 0 && !(g->rk_fp32 ? (const void*)q32 : (const void*)q64))
         return mr_fail(ctx, MR_ERR_STATE, "%s: the ranking's trace vector is gone", who);
     // the P_rs rows of traces with w_t = 0: only where P_rs is given apart from P_sr (never fused)
     const bool rs_rows = !g->rs_is_sr && !g->fused && K > 0 && g->sub[(K + 1) & 1].p;
-    hipLaunchKernelGGL(k_trace_rank, dim3(cdiv(T, EX_T)), dim3(EX_T), 0, ctx->stream, q64, q32,
-                       g->fused ? (const int32_t*)g->tperm.p : (const int32_t*)nullptr, g->w_t.p, g->c_t.p, g->mslot.p, K, T,
-                       1.0 / (double)((int64_t)g->N + (int64_t)T), rs_rows ? (const int64_t*)g->rs_off.p : (const int64_t*)nullptr,
-                       (const int32_t*)g->rs_ops.p, (const double*)g->sub[(K + 1) & 1].p, g->rk_d, g->trank.p);
+    const int64_t T_all = shard && g->T_all > 0 ? g->T_all : (int64_t)T;
+    if (T > 0)   // (a shard may hold no trace)
+        hipLaunchKernelGGL(k_trace_rank, dim3(cdiv(T, EX_T)), dim3(EX_T), 0, ctx->stream, q64, q32,
+                           g->fused ? (const int32_t*)g->tperm.p : (const int32_t*)nullptr, g->w_t.p, g->c_t.p, g->mslot.p, K, T,
+                           1.0 / (double)((int64_t)g->N + T_all), rs_rows ? (const int64_t*)g->rs_off.p : (const int64_t*)nullptr,
+                           (const int32_t*)g->rs_ops.p, (const double*)g->sub[(K + 1) & 1].p, g->rk_d, g->trank.p);
     MR_TRY_HIP(ctx, hipGetLastError());
     g->trank_ok = true;
     return MR_OK;
 }
+int mr_trace_rank_ensure(mr_ctx* ctx, mr_graph* g, const char* who) { return trace_rank_fill(ctx, g, who, false); }
 
 // request_ranking_vector after the last ranking's iterations (pagerank.py:119-127), in the graph's trace order
 extern "C" int mr_graph_trace_rank(mr_graph* g, double* r) {
@@ -670,6 +679,65 @@ extern "C" int mr_graph_trace_rank(mr_graph* g, double* r) {
     MR_TRY(mr_trace_rank_ensure(ctx, g, "mr_graph_trace_rank"));
     MR_TRY(g->trank.download(ctx, r, (size_t)g->T));
     MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MR_OK;
+}
+
+// distinct ops for the kernels; request i is answered from slot[i]
+static void ex_request(const int32_t* ops, int32_t n_ops, ExReq& rq, int32_t* slot) {
+    memset(&rq, 0, sizeof rq);
+    for (int32_t i = 0; i < n_ops; ++i) {
+        int32_t u = 0;
+        while (u < rq.n && rq.op[u] != ops[i]) ++u;
+        if (u == rq.n) rq.op[rq.n++] = ops[i];
+        slot[i] = u;
+    }
+}
+// A graph's own lists for a request: k_ex_select over its traces, k_ex_merge over the blocks, into ob --
+// [nu * m] score bits, then as int32 [nu * m] traces, [nu] counts and (dk) [nu * m] class sizes.  The
+// scratch lives here until the caller's sync.  A graph without traces (an empty shard): zero counts.
+struct ExLists {
+    DBuf<unsigned long long> ps, ob;
+    DBuf<int32_t> pt, pk, pm;
+    size_t nm = 0, ob_words = 0;
+};
+static int ex_local_lists(mr_ctx* ctx, mr_graph* g, const ExReq& rq, int32_t m, bool dk, ExLists& L) {
+    const int32_t T = g->T, nu = rq.n;
+    const size_t nm = L.nm = (size_t)nu * m;
+    L.ob_words = nm + (nm + (size_t)nu + (dk ? nm : 0) + 1) / 2;
+    hipStream_t st = ctx->stream;
+    // the P_sr rows, trace-major: operation_trace as uploaded, else the one incidence of P_rs == P_sr
+    // (T == 0, an empty shard: one block that reads nothing and writes empty lists)
+    const int64_t* off = g->rs_is_sr ? g->rs_off.p : g->srt_off.p;
+    if (!off && T > 0) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_exemplars: the graph has no trace-major incidence");
+    int64_t nb = std::min<int64_t>(cdiv(std::max(T, 1), EX_T), 2 * (int64_t)ex_num_cus());
+    if (const char* e = getenv("MR_EX_BLOCKS"))   // (test knob, read per call)
+        if (atoi(e) > 0) nb = atoi(e);
+    nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
+    const int32_t per = cdiv(std::max(T, 1), nb);
+    MR_TRY(L.ps.alloc(ctx, (size_t)nb * nm));
+    MR_TRY(L.pt.alloc(ctx, (size_t)nb * nm));
+    if (dk) {
+        if (!g->kind.p || !g->krep.p) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_exemplars_ex: the graph's kinds are gone");
+        MR_TRY(L.pk.alloc(ctx, (size_t)nb * nm));
+        MR_TRY(L.pm.alloc(ctx, (size_t)nb * nm));
+    }
+    MR_TRY(L.ob.alloc(ctx, L.ob_words));
+    const int32_t* krep = dk ? (const int32_t*)g->krep.p : (const int32_t*)nullptr;
+    const double* kind = dk ? (const double*)g->kind.p : (const double*)nullptr;
+    auto sel16 = dk ? k_ex_select<uint16_t, true> : k_ex_select<uint16_t, false>;
+    auto sel32 = dk ? k_ex_select<int32_t, true> : k_ex_select<int32_t, false>;
+    if (g->rs_is_sr && g->rs16.p)
+        hipLaunchKernelGGL(sel16, dim3((unsigned)nb), dim3(EX_T), 0, st, off, (const uint16_t*)g->rs16.p,
+                           (const double*)g->trank.p, T, per, rq, m, L.ps.p, L.pt.p, krep, kind, L.pk.p, L.pm.p);
+    else
+        hipLaunchKernelGGL(sel32, dim3((unsigned)nb), dim3(EX_T), 0, st, off,
+                           g->rs_is_sr ? (const int32_t*)g->rs_ops.p : (const int32_t*)g->srt_ops.p,
+                           (const double*)g->trank.p, T, per, rq, m, L.ps.p, L.pt.p, krep, kind, L.pk.p, L.pm.p);
+    int32_t* ot = (int32_t*)(L.ob.p + nm);
+    hipLaunchKernelGGL(dk ? k_ex_merge<true> : k_ex_merge<false>, dim3((unsigned)nu), dim3(EX_T), 0, st,
+                       (const unsigned long long*)L.ps.p, (const int32_t*)L.pt.p, (int32_t)nb, nu, m, L.ob.p, ot, ot + nm,
+                       (const int32_t*)L.pk.p, (const int32_t*)L.pm.p, ot + nm + nu);
+    MR_TRY_HIP(ctx, hipGetLastError());
     return MR_OK;
 }
 
@@ -691,58 +759,15 @@ extern "C" int mr_graph_exemplars_ex(mr_graph* g, const int32_t* ops, int32_t n_
         if (ops[i] < 0 || ops[i] >= g->N) return mr_fail(ctx, MR_ERR_ARG, "mr_graph_exemplars: op %d outside [0, %d)", ops[i], g->N);
     MR_TRY(mr_trace_rank_ensure(ctx, g, "mr_graph_exemplars"));
     if (dk) MR_TRY(mr_kind_reps_ensure(ctx, g));
-    // distinct ops for the kernels; request i is answered from slot[i]
     ExReq rq;
-    memset(&rq, 0, sizeof rq);
     int32_t slot[EX_MAXOPS];
-    for (int32_t i = 0; i < n_ops; ++i) {
-        int32_t u = 0;
-        while (u < rq.n && rq.op[u] != ops[i]) ++u;
-        if (u == rq.n) rq.op[rq.n++] = ops[i];
-        slot[i] = u;
-    }
-    const int32_t T = g->T, nu = rq.n;
-    // the P_sr rows, trace-major: operation_trace as uploaded, else the one incidence of P_rs == P_sr
-    const int64_t* off = g->rs_is_sr ? g->rs_off.p : g->srt_off.p;
-    if (!off) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_exemplars: the graph has no trace-major incidence");
-    int64_t nb = std::min<int64_t>(cdiv(std::max(T, 1), EX_T), 2 * (int64_t)ex_num_cus());
-    if (const char* e = getenv("MR_EX_BLOCKS"))   // (test knob, read per call)
-        if (atoi(e) > 0) nb = atoi(e);
-    nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
-    const int32_t per = cdiv(std::max(T, 1), nb);
-    DBuf<unsigned long long> ps;
-    DBuf<int32_t> pt, pk, pm;
-    // [nu * m] score bits, then as int32 [nu * m] traces, [nu] counts and (dk) [nu * m] class sizes
-    DBuf<unsigned long long> ob;
-    const size_t nm = (size_t)nu * m;
-    const size_t ob_words = nm + (nm + (size_t)nu + (dk ? nm : 0) + 1) / 2;
-    MR_TRY(ps.alloc(ctx, (size_t)nb * nm));
-    MR_TRY(pt.alloc(ctx, (size_t)nb * nm));
-    if (dk) {
-        if (!g->kind.p || !g->krep.p) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_exemplars_ex: the graph's kinds are gone");
-        MR_TRY(pk.alloc(ctx, (size_t)nb * nm));
-        MR_TRY(pm.alloc(ctx, (size_t)nb * nm));
-    }
-    MR_TRY(ob.alloc(ctx, ob_words));
-    hipStream_t st = ctx->stream;
-    const int32_t* krep = dk ? (const int32_t*)g->krep.p : (const int32_t*)nullptr;
-    const double* kind = dk ? (const double*)g->kind.p : (const double*)nullptr;
-    auto sel16 = dk ? k_ex_select<uint16_t, true> : k_ex_select<uint16_t, false>;
-    auto sel32 = dk ? k_ex_select<int32_t, true> : k_ex_select<int32_t, false>;
-    if (g->rs_is_sr && g->rs16.p)
-        hipLaunchKernelGGL(sel16, dim3((unsigned)nb), dim3(EX_T), 0, st, off, (const uint16_t*)g->rs16.p,
-                           (const double*)g->trank.p, T, per, rq, m, ps.p, pt.p, krep, kind, pk.p, pm.p);
-    else
-        hipLaunchKernelGGL(sel32, dim3((unsigned)nb), dim3(EX_T), 0, st, off,
-                           g->rs_is_sr ? (const int32_t*)g->rs_ops.p : (const int32_t*)g->srt_ops.p,
-                           (const double*)g->trank.p, T, per, rq, m, ps.p, pt.p, krep, kind, pk.p, pm.p);
-    int32_t* ot = (int32_t*)(ob.p + nm);
-    hipLaunchKernelGGL(dk ? k_ex_merge<true> : k_ex_merge<false>, dim3((unsigned)nu), dim3(EX_T), 0, st,
-                       (const unsigned long long*)ps.p, (const int32_t*)pt.p, (int32_t)nb, nu, m, ob.p, ot, ot + nm,
-                       (const int32_t*)pk.p, (const int32_t*)pm.p, ot + nm + nu);
-    MR_TRY_HIP(ctx, hipGetLastError());
+    ex_request(ops, n_ops, rq, slot);
+    const int32_t nu = rq.n;
+    ExLists L;
+    MR_TRY(ex_local_lists(ctx, g, rq, m, dk, L));
+    const size_t nm = L.nm, ob_words = L.ob_words;
     unsigned char* h = nullptr;   // <= 64 * 32 * 16 + 64 * 4 + 8 bytes: one pinned read-back
-    MR_TRY(mr_read_bytes(ctx, ob.p, ob_words * sizeof(unsigned long long), &h));
+    MR_TRY(mr_read_bytes(ctx, L.ob.p, ob_words * sizeof(unsigned long long), &h));
     const double* hs = (const double*)h;
     const int32_t* hts = (const int32_t*)(h + nm * sizeof(double));
     const int32_t* hn = hts + nm;
@@ -759,6 +784,210 @@ extern "C" int mr_graph_exemplars_ex(mr_graph* g, const int32_t* ops, int32_t n_
 extern "C" int mr_graph_exemplars(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m, int32_t* out_trace,
                                   double* out_score, int32_t* out_n) {
     return mr_graph_exemplars_ex(g, ops, n_ops, m, 0u, out_trace, out_score, out_n, nullptr);
+}
+
+// ---------------------------------------------------------------- trace shards
+// The same two answers after mr_pagerank_sharded(_converge), where each rank holds only its own traces.
+// The trace vector needs no exchange: q[K & 1] is this rank's, the ring's r half already holds the
+// WHOLE graph's M_r(K) (every rank's r' maximum rides the per-iteration all-reduce).  The exemplars
+// are each rank's own lists (k_ex_select + k_ex_merge, as on a whole graph), then
+//   k_ex_shard_pack    every list entry as a (score bits, global trace id) record into a send buffer of
+//                      FIXED size -- the maxima EX_MAXOPS x EX_MAXM records, EX_MAXOPS counts and a
+//                      header (n_ops, m, the ranking's iterations and precision, a hash of the ops) --
+//                      so that a rank asking something else cannot desynchronise the all-gather
+//   one mr_coll_allgather
+//   k_ex_shard_merge   a block per op, a thread per rank: m rounds of "best head" over the ranks'
+//                      sorted lists, score bits descending, global id ascending; block 0 compares the
+//                      headers.  A trace lies on one rank, so the winner's id names its list.
+constexpr int XS_HDR = 8;                                                       // header words
+constexpr int XS_WORDS = XS_HDR + EX_MAXOPS + 2 * EX_MAXOPS * EX_MAXM;          // u64 words a rank sends
+struct XsHdr {
+    unsigned long long w[XS_HDR];
+};
+
+__global__ void __launch_bounds__(EX_T) k_ex_shard_pack(const unsigned long long* __restrict__ os,
+                                                        const int32_t* __restrict__ ot, const int32_t* __restrict__ on,
+                                                        int32_t nu, int32_t m, const int32_t* __restrict__ trace_code,
+                                                        long long base, XsHdr hdr, unsigned long long* __restrict__ send) {
+    const int32_t i = (int32_t)blockIdx.x * EX_T + (int32_t)threadIdx.x;   // entry (u, j) of the maxima
+    if (i >= EX_MAXOPS * EX_MAXM) return;
+    if (i < XS_HDR) send[i] = hdr.w[i];
+    const int32_t u = i / EX_MAXM, j = i % EX_MAXM;
+    const int32_t c = u < nu ? min(on[u], m) : 0;
+    if (j == 0) send[XS_HDR + u] = (unsigned long long)c;
+    ulonglong2 rec = make_ulonglong2(0ull, ~0ull);   // absent: (0.0, -1)
+    if (j < c) {
+        const int32_t t = ot[(size_t)u * m + j];
+        rec.x = os[(size_t)u * m + j];
+        rec.y = (unsigned long long)(trace_code ? (long long)trace_code[t] : base + t);
+    }
+    *reinterpret_cast<ulonglong2*>(send + XS_HDR + EX_MAXOPS + 2 * (size_t)i) = rec;   // (16-byte aligned: an even word)
+}
+
+__device__ __forceinline__ bool xs_before(unsigned long long s, long long g, unsigned long long s2, long long g2) {
+    return s > s2 || (s == s2 && g < g2);
+}
+// recv: R ranks' send buffers; os / og [nu * m], on [nu], bad [1] (headers differ)
+__global__ void __launch_bounds__(EX_T) k_ex_shard_merge(const unsigned long long* __restrict__ recv, int32_t R, int32_t m,
+                                                         unsigned long long* __restrict__ os, long long* __restrict__ og,
+                                                         int32_t* __restrict__ on, int32_t* __restrict__ bad) {
+    __shared__ unsigned long long rs[EX_T / WAVE];
+    __shared__ long long rg[EX_T / WAVE];
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const int32_t u = (int32_t)blockIdx.x;
+    const bool has = tid < R;   // (R <= EX_T: the host checks)
+    const unsigned long long* mine = recv + (size_t)(has ? tid : 0) * XS_WORDS;
+    if (u == 0) {   // every rank asked the same of the same ranking
+        int diff = 0;
+        if (has)
+            for (int k = 0; k < XS_HDR; ++k) diff |= mine[k] != recv[k];
+        diff = __syncthreads_or(diff);
+        if (tid == 0) *bad = diff;
+    }
+    // this thread's list: rank tid's entries of op u, sorted (the layout does not depend on m)
+    const ulonglong2* list = reinterpret_cast<const ulonglong2*>(mine + XS_HDR + EX_MAXOPS) + (size_t)u * EX_MAXM;
+    const int32_t c = has ? (int32_t)min(mine[XS_HDR + u], (unsigned long long)EX_MAXM) : 0;
+    int32_t hp = 0;
+    unsigned long long hs = 0ull;
+    long long hg = -1;   // (-1: the list is used up)
+    if (hp < c) {
+        const ulonglong2 e = list[0];
+        hs = e.x;
+        hg = (long long)e.y;
+    }
+    int32_t cnt = 0;
+    for (int32_t j = 0; j < m; ++j) {
+        unsigned long long bs = hs;
+        long long bg = hg;
+#pragma unroll
+        for (int d = WAVE / 2; d >= 1; d >>= 1) {
+            const unsigned long long s2 = __shfl_xor(bs, d, WAVE);
+            const long long g2 = __shfl_xor(bg, d, WAVE);
+            if (g2 >= 0 && (bg < 0 || xs_before(s2, g2, bs, bg))) {
+                bs = s2;
+                bg = g2;
+            }
+        }
+        __syncthreads();   // (the previous round's reads of rs / rg)
+        if (lane == 0) {
+            rs[wv] = bs;
+            rg[wv] = bg;
+        }
+        __syncthreads();
+        bs = rs[0];
+        bg = rg[0];
+        for (int w = 1; w < EX_T / WAVE; ++w)
+            if (rg[w] >= 0 && (bg < 0 || xs_before(rs[w], rg[w], bs, bg))) {
+                bs = rs[w];
+                bg = rg[w];
+            }
+        if (bg < 0) break;   // (uniform) every list is used up
+        if (tid == 0) {
+            os[(size_t)u * m + j] = bs;
+            og[(size_t)u * m + j] = bg;
+        }
+        ++cnt;
+        if (hg == bg) {   // this rank's head won: its next entry
+            ++hp;
+            hs = 0ull;
+            hg = -1;
+            if (hp < c) {
+                const ulonglong2 e = list[hp];
+                hs = e.x;
+                hg = (long long)e.y;
+            }
+        }
+    }
+    for (int32_t j = cnt + tid; j < m; j += EX_T) {
+        os[(size_t)u * m + j] = 0ull;
+        og[(size_t)u * m + j] = -1;
+    }
+    if (tid == 0) on[u] = cnt;
+}
+
+// r of this rank's traces after the last sharded ranking, normalised by the whole graph's M_r(K), and
+// the traces' global ids (the codes of a span-built shard, else t_base + t: shard_exchange)
+extern "C" int mr_graph_trace_rank_sharded(mr_graph* g, double* r, int64_t* gid) {
+    if (!g) return MR_ERR_ARG;
+    mr_ctx* ctx = g->ctx;
+    if (!r) return mr_fail(ctx, MR_ERR_ARG, "mr_graph_trace_rank_sharded: null argument");
+    MR_TRY(trace_rank_fill(ctx, g, "mr_graph_trace_rank_sharded", true));
+    const size_t T = (size_t)g->T;
+    std::vector<int32_t> code;
+    MR_TRY(g->trank.download(ctx, r, T));
+    if (gid && g->shard_built && T) {
+        if (!g->trace_code.p) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_trace_rank_sharded: the graph's trace codes are gone");
+        code.resize(T);
+        MR_TRY(g->trace_code.download(ctx, code.data(), T));
+    }
+    MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (gid)
+        for (size_t t = 0; t < T; ++t) gid[t] = g->shard_built ? (int64_t)code[t] : g->t_base + (int64_t)t;
+    return MR_OK;
+}
+
+extern "C" int mr_graph_exemplars_sharded(mr_graph* g, const int32_t* ops, int32_t n_ops, int32_t m, int64_t* out_trace,
+                                          double* out_score, int32_t* out_n) {
+    if (!g) return MR_ERR_ARG;
+    mr_ctx* ctx = g->ctx;
+    const char* who = "mr_graph_exemplars_sharded";
+    if (!ops || !out_trace || !out_score || !out_n) return mr_fail(ctx, MR_ERR_ARG, "%s: null argument", who);
+    if (n_ops < 1 || n_ops > EX_MAXOPS) return mr_fail(ctx, MR_ERR_ARG, "%s: n_ops outside 1..%d", who, EX_MAXOPS);
+    if (m < 1 || m > EX_MAXM) return mr_fail(ctx, MR_ERR_ARG, "%s: m outside 1..%d", who, EX_MAXM);
+    for (int32_t i = 0; i < n_ops; ++i)
+        if (ops[i] < 0 || ops[i] >= g->N) return mr_fail(ctx, MR_ERR_ARG, "%s: op %d outside [0, %d)", who, ops[i], g->N);
+    const int R = ctx->nranks;
+    if (R > EX_T) return mr_fail(ctx, MR_ERR_ARG, "%s: more than %d ranks", who, EX_T);
+    MR_TRY(trace_rank_fill(ctx, g, who, true));
+    if (g->shard_built && g->T > 0 && !g->trace_code.p) return mr_fail(ctx, MR_ERR_STATE, "%s: the graph's trace codes are gone", who);
+    ExReq rq;
+    int32_t slot[EX_MAXOPS];
+    ex_request(ops, n_ops, rq, slot);
+    const int32_t nu = rq.n;
+    ExLists L;
+    MR_TRY(ex_local_lists(ctx, g, rq, m, false, L));
+    XsHdr hdr;
+    memset(&hdr, 0, sizeof hdr);
+    unsigned long long hash = 1469598103934665603ull;   // FNV-1a over the request's ops, in order
+    for (int32_t i = 0; i < n_ops; ++i) hash = (hash ^ (uint32_t)ops[i]) * 1099511628211ull;
+    hdr.w[0] = (unsigned long long)n_ops;
+    hdr.w[1] = (unsigned long long)m;
+    hdr.w[2] = (unsigned long long)g->rk_iters;
+    hdr.w[3] = g->rk_fp32 ? 1ull : 0ull;
+    hdr.w[4] = hash;
+    hipStream_t st = ctx->stream;
+    const size_t nm = L.nm;
+    // out: [nu * m] score bits, [nu * m] global ids, then as int32 [nu] counts and the header word
+    const size_t out_words = 2 * nm + ((size_t)nu + 1 + 1) / 2;
+    DBuf<unsigned long long> send, recv, out;
+    MR_TRY(send.alloc(ctx, XS_WORDS));
+    MR_TRY(recv.alloc(ctx, (size_t)XS_WORDS * R));
+    MR_TRY(out.alloc(ctx, out_words));
+    const int32_t* lt = (const int32_t*)(L.ob.p + nm);
+    hipLaunchKernelGGL(k_ex_shard_pack, dim3(cdiv(EX_MAXOPS * EX_MAXM, EX_T)), dim3(EX_T), 0, st,
+                       (const unsigned long long*)L.ob.p, lt, lt + nm, nu, m,
+                       g->shard_built ? (const int32_t*)g->trace_code.p : (const int32_t*)nullptr, (long long)g->t_base, hdr,
+                       send.p);
+    MR_TRY_HIP(ctx, hipGetLastError());
+    MR_TRY(mr_coll_allgather(ctx, send.p, recv.p, XS_WORDS, MR_DT_U64));
+    int32_t* oi = (int32_t*)(out.p + 2 * nm);
+    hipLaunchKernelGGL(k_ex_shard_merge, dim3((unsigned)nu), dim3(EX_T), 0, st, (const unsigned long long*)recv.p, (int32_t)R, m,
+                       out.p, (long long*)(out.p + nm), oi, oi + nu);
+    MR_TRY_HIP(ctx, hipGetLastError());
+    unsigned char* h = nullptr;   // <= 64 * 32 * 16 + 65 * 4 + 4 bytes: one pinned read-back
+    MR_TRY(mr_read_bytes(ctx, out.p, out_words * sizeof(unsigned long long), &h));
+    const double* hs = (const double*)h;
+    const int64_t* hg = (const int64_t*)(h + nm * sizeof(double));
+    const int32_t* hn = (const int32_t*)(h + 2 * nm * sizeof(double));
+    if (hn[nu])
+        return mr_fail(ctx, MR_ERR_ARG, "%s: the ranks' requests differ (ops, m) or follow different rankings", who);
+    for (int32_t i = 0; i < n_ops; ++i) {
+        const size_t u = (size_t)slot[i];
+        memcpy(out_score + (size_t)i * m, hs + u * m, (size_t)m * sizeof(double));
+        memcpy(out_trace + (size_t)i * m, hg + u * m, (size_t)m * sizeof(int64_t));
+        out_n[i] = hn[u];
+    }
+    return MR_OK;
 }
 
 // The window batch's exemplar rows (mr_internal.h): every layout-order window of the call in one

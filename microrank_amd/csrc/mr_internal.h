@@ -282,6 +282,7 @@ struct mr_graph {
     bool traces_nonempty = true;   // every trace has an op (span-built graphs; checked at upload)
     bool force_tile = false;       // the ranks of a sharded graph agreed on the tile path
     int64_t T_all = 0;             // traces over all shards (0: this graph is whole)
+    int64_t t_base = 0;            // traces of the lower ranks: the global id of this shard's trace 0 (shard_exchange)
     bool sharded_done = false;     // mr_pagerank_sharded's graph-level exchange has run
     bool shard_built = false;      // built by mr_graph_build_sharded (mr_pagerank_converge rejects it)
     DBuf<uint64_t> fx_part;   // [n_blocks * N]
@@ -322,6 +323,7 @@ struct mr_graph {
     // the last successful ranking of a public entry (mr_exemplar.hip reads what it left behind: q,
     // the maxima ring, c_t); cleared by whatever re-sets the iteration state without ranking
     bool rk_ok = false, rk_fp32 = false, rk_kc = false;   // rk_kc: asked with MR_PR_KIND_COMPRESS
+    bool rk_sharded = false;     // a sharded ranking: q holds this rank's traces, the ring the whole graph's maxima
     int32_t rk_iters = 0;        // iterations run (mr_pagerank_converge: where it stopped)
     double rk_d = 0.0;           // its damping factor
     DBuf<double> trank;          // [T] max-normalised r of that ranking, by trace (built on first use)

@@ -1981,6 +1981,9 @@ struct Converge {
     unsigned long long* resid_dev;   // [ng * max_iters] bits of the residuals, zeroed by the attempt
     double* resid;                   // [ng * max_iters] host: the history, entries >= iters_done 0.0
     int iters_done;                  // out: iterations every graph ran
+    // a shard (mr_pagerank_sharded_converge): before each read the stretch's words meet in a MAX over
+    // the ranks, so every rank reads the same words and takes the same decision
+    bool agree = false;
 };
 
 // A graph's descriptor, part 1: its arrays and sizes, field for field
@@ -2303,6 +2306,8 @@ static int iterate_to_tol(mr_ctx* ctx, mr_graph* const* gs, int ng, bool fp32, d
     while (it < cv->max_iters) {
         const int end = cv->tol > 0.0 ? std::min(it + cv->check_every, cv->max_iters) : cv->max_iters;
         MR_TRY(iterate(ctx, gs, ng, fp32, d, alpha, it, end, plan, hv, dv, L, cv));
+        // (one graph: the stretch's words are contiguous.  The fallback collective, not the peer regions)
+        if (cv->agree) MR_TRY(mr_coll_allreduce(ctx, cv->resid_dev + it, end - it, MR_DT_U64, 1));
         it = end;
         if (bytes <= MR_PIN_BYTES) {
             unsigned char* hp = nullptr;
@@ -2337,9 +2342,11 @@ static int decode_error_words(mr_ctx* ctx, const int32_t* words, const int* anom
 // One attempt with kind-hash seed `seed`; *collided reports a 64-bit key collision found by the
 // exact verification (k_kind_verify / k_sh_kind_check), after which the caller retries.
 // as: enqueue only (window groups); mr_pagerank_async_finish reads the error words
-// cv: a convergence request (iters = its max_iters; never with `as` or a sharded graph) -- no pf
+// cv: a convergence request (iters = its max_iters; never with `as`) -- no pf
 // launches: the next launch's prologue would finish an iteration and then clear the ring slot the
-// residual reads; the k_fx_b form's results are bitwise the pf form's
+// residual reads; the k_fx_b form's results are bitwise the pf form's.  On a shard (cv->agree) k_resid
+// runs unchanged: k_fx_b / k_iter_b mode 2 leave spb[(it+1)&1] and the s half of ring slot (it+1)%3
+// replicated on every rank, and the words still meet in a MAX before they are read
 // last_resid ([ng] host; as: as->report): the residual of the last iteration alone, one k_resid
 // behind the iterations, in every launch form -- nothing runs after the closing k_fx_b, so the ring
 // slots and both vectors it reads are intact; its words share the error words' read
@@ -2432,6 +2439,7 @@ static int pagerank_attempt(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly
             gs[i]->rk_ok = true;
             gs[i]->rk_fp32 = fp32;
             gs[i]->rk_kc = false;
+            gs[i]->rk_sharded = sharded;
             gs[i]->rk_iters = iters;
             gs[i]->rk_d = d;
         }
@@ -2573,9 +2581,9 @@ int mr_pagerank_batch_report(mr_ctx* ctx, mr_graph* const* gs, const int* anomal
     return MR_OK;
 }
 
-extern "C" int mr_pagerank_sharded(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int iters,
-                                   int precision, uint32_t flags) {
-    if (!ctx || !g || g->ctx != ctx) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded: bad handles");
+// What a sharded ranking needs before its attempt: the graph-level exchange (once per graph) and the
+// per-iteration all-reduce buffer.  Collective.
+static int sharded_prologue(mr_ctx* ctx, mr_graph* g) {
     if (!mr_coll_ready(ctx) && ctx->nranks != 1) return mr_fail(ctx, MR_ERR_COMM, "no collective backend");
     MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     if (!g->sharded_done) {   // the graph-level exchange happens once per graph
@@ -2600,5 +2608,69 @@ extern "C" int mr_pagerank_sharded(mr_ctx* ctx, mr_graph* g, int anomaly, double
     // the per-iteration all-reduce buffer: the per-op sums, then one r' max slot per rank
     if (g->fused) MR_TRY(g->fx_limb.alloc(ctx, 2 * (size_t)g->N + (size_t)ctx->nranks));   // fixed-point limbs
     else MR_TRY(g->op_sum.alloc(ctx, (size_t)g->N + (size_t)ctx->nranks));                  // tile path: fp64 sums
+    return MR_OK;
+}
+
+extern "C" int mr_pagerank_sharded(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int iters,
+                                   int precision, uint32_t flags) {
+    if (!ctx || !g || g->ctx != ctx) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded: bad handles");
+    MR_TRY(sharded_prologue(ctx, g));
     return mr_pagerank_batch_impl(ctx, &g, &anomaly, 1, d, alpha, iters, precision, flags, true);
+}
+
+// mr_pagerank_sharded with mr_pagerank_converge's history and stop (README.md:37; pagerank.py:117's
+// fixed count).  The ranks first compare their requests (a differing count of checks would hang them),
+// then agree on every check's words (Converge::agree).
+extern "C" int mr_pagerank_sharded_converge(mr_ctx* ctx, mr_graph* g, int anomaly, double d, double alpha, int max_iters,
+                                            double phi, int precision, uint32_t flags, double tol, int check_every,
+                                            int32_t* iters_done, double* resid, int32_t* converged_at) {
+    if (!ctx || !g || g->ctx != ctx || !iters_done || !resid)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: bad handles or null arguments");
+    if (!mr_coll_ready(ctx) && ctx->nranks != 1) return mr_fail(ctx, MR_ERR_COMM, "no collective backend");
+    MR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const int R = ctx->nranks;
+    if (mr_coll_ready(ctx) && R > 1) {   // the same request on every rank, before anything depends on it
+        constexpr int NW = 9;
+        auto bits = [](double x) { uint64_t b; memcpy(&b, &x, sizeof b); return b; };
+        const uint64_t mine[NW] = {(uint64_t)(int64_t)max_iters, (uint64_t)(int64_t)check_every, bits(tol), bits(d), bits(alpha),
+                                   bits(phi), (uint64_t)(int64_t)precision, (uint64_t)flags, (uint64_t)(anomaly != 0)};
+        DBuf<uint64_t> send, recv;
+        std::vector<uint64_t> all((size_t)NW * R);
+        MR_TRY(send.upload(ctx, mine, NW));
+        MR_TRY(recv.alloc(ctx, (size_t)NW * R));
+        MR_TRY(mr_coll_allgather(ctx, send.p, recv.p, NW, MR_DT_U64));
+        MR_TRY(recv.download(ctx, all.data(), all.size()));
+        MR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int r = 0; r < R; ++r)
+            if (memcmp(all.data() + (size_t)NW * r, all.data(), sizeof mine) != 0)
+                return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: rank %d's request differs from rank 0's "
+                               "(max_iters, check_every, tol, d, alpha, phi, precision, flags, anomaly)", r);
+    }
+    if (max_iters < 1 || check_every < 1)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: max_iters, check_every < 1");
+    if (!(tol >= 0.0)) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: tol negative or NaN");
+    if (!(phi > 0.0)) return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: phi <= 0");
+    if (flags & MR_PR_KIND_COMPRESS)
+        return mr_fail(ctx, MR_ERR_ARG, "mr_pagerank_sharded_converge: MR_PR_KIND_COMPRESS is not supported");
+    MR_TRY(sharded_prologue(ctx, g));
+    DBuf<unsigned long long> rd;
+    MR_TRY(rd.alloc(ctx, (size_t)max_iters));
+    Converge cv{tol, check_every, max_iters, rd.p, resid, 0, true};
+    g->phi = phi;
+    constexpr int ATTEMPTS = 4;   // (mr_pagerank_batch_impl's seed sequence)
+    int rc = MR_OK;
+    bool collided = true;
+    for (int a = 0; a < ATTEMPTS && rc == MR_OK && collided; ++a)
+        rc = pagerank_attempt(ctx, &g, &anomaly, 1, d, alpha, max_iters, precision, flags, true, kind_seed(a), kind_hmask(a),
+                              &collided, nullptr, &cv);
+    g->phi = 0.5;
+    MR_TRY(rc);
+    if (collided) return mr_fail(ctx, MR_ERR_STATE, "trace-kind hash collision under %d seeds", ATTEMPTS);
+    *iters_done = cv.iters_done;
+    if (converged_at) {
+        *converged_at = -1;
+        for (int k = 0; k < cv.iters_done && *converged_at < 0; ++k)
+            if (resid[k] <= tol) *converged_at = k + 1;
+    }
+    return MR_OK;
 }

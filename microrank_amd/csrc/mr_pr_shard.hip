@@ -290,17 +290,25 @@ int shard_exchange(mr_ctx* ctx, mr_graph* g) {
     MR_TRY(mr_coll_allreduce(ctx, g->nchild.p, N, MR_DT_I32, 0));
     MR_TRY(mr_coll_allreduce(ctx, g->cov.p, N, MR_DT_I32, 0));
     if (N) hipLaunchKernelGGL(k_op_consts, dim3(cdiv(N, 256)), dim3(256), 0, st, g->len_o.p, g->nchild.p, g->u_o.p, g->pw.p, N);
-    DBuf<int64_t> sc;
-    MR_TRY(sc.alloc(ctx, 2));
+    const int R = ctx->nranks;
+    DBuf<int64_t> sc, tc;
     int64_t h[2] = {(int64_t)g->T, g->E};
     MR_TRY(sc.upload(ctx, h, 2));
-    MR_TRY(mr_coll_allreduce(ctx, sc.p, 1, MR_DT_I64, 0));       // traces over all ranks
+    MR_TRY(tc.alloc(ctx, (size_t)R));
+    // every rank's trace count: their sum is the whole graph's T, the lower ranks' the global id of
+    // this shard's first trace (mr_graph_trace_rank_sharded)
+    MR_TRY(mr_coll_allgather(ctx, sc.p, tc.p, 1, MR_DT_I64));
     MR_TRY(mr_coll_allreduce(ctx, sc.p + 1, 1, MR_DT_I64, 1));   // largest local edge list
+    std::vector<int64_t> tr((size_t)R);
+    MR_TRY(tc.download(ctx, tr.data(), (size_t)R));
     MR_TRY(sc.download(ctx, h, 2));
     MR_TRY_HIP(ctx, hipStreamSynchronize(st));
-    g->T_all = h[0];
+    g->T_all = g->t_base = 0;
+    for (int r = 0; r < R; ++r) {
+        if (r < ctx->rank) g->t_base += tr[(size_t)r];
+        g->T_all += tr[(size_t)r];
+    }
     const int64_t Emax = std::max<int64_t>(h[1], 1);
-    const int R = ctx->nranks;
     const int nb = std::max(1, bits_for((uint64_t)std::max(N - 1, 0)));
     const uint64_t pad = 1ull << (2 * nb);   // above every real key
     DBuf<uint64_t> send, recv;

@@ -134,3 +134,66 @@ def build_graph(dev_spans, trace_mask) -> "DeviceGraph":
     trace_code = np.empty(t.value, np.int32)
     ctx.check(lib.mr_graph_nodes(h, ptr(node_podop, C.c_int32), ptr(trace_code, C.c_int32)), "mr_graph_nodes")
     return DeviceGraph(ctx, h, node_podop, trace_code, n.value, t.value)
+
+
+def sharded_converge(dg, anomaly: bool, *, tol: float, max_iters: int = 200, check_every: int = 5, d: float = 0.85,
+                     alpha: float = 0.01, phi: float = 0.5, precision: str = "fp64"):
+    """:func:`sharded_pagerank` to a tolerance (mr_pagerank_sharded_converge; collective: every rank
+    calls it with the same arguments, differing ones raise ValueError on every rank).  Every
+    iteration's residual max|s_k - s_{k-1}| of the WHOLE graph is recorded on the device; at every
+    check (check_every iterations, and at max_iters) the ranks agree on the words and stop where the
+    last residual is <= tol.  Returns (weights, coverage, {"iters", "residuals", "converged_at"}), the
+    dict as DeviceGraph.converge's and identical on every rank; the weights are those of
+    ``sharded_pagerank(iters=iters)``, bit for bit."""
+    from .graph import check_converge_args
+
+    check_converge_args(tol, max_iters, check_every, phi)
+    lib = _lib.load()
+    prec = _lib.MR_FP32 if precision == "fp32" else _lib.MR_FP64
+    done = C.c_int32(0)
+    conv = C.c_int32(-1)
+    resid = np.zeros(int(max_iters), np.float64)
+    dg.ctx.check(lib.mr_pagerank_sharded_converge(dg.ctx.h, dg.h, int(bool(anomaly)), float(d), float(alpha),
+                                                  int(max_iters), float(phi), prec, 0, float(tol), int(check_every),
+                                                  C.byref(done), ptr(resid, C.c_double), C.byref(conv)),
+                 "mr_pagerank_sharded_converge")
+    k = int(done.value)
+    w, cov = dg.fetch()
+    return w, cov, {"iters": k, "residuals": resid[:k].copy(), "converged_at": int(conv.value) if conv.value > 0 else None}
+
+
+def sharded_trace_rank(dg):
+    """The trace half of the last sharded ranking for THIS rank's traces (mr_graph_trace_rank_sharded;
+    not collective): (gid int64[T], r float64[T]).  r is normalised by the whole graph's maximum, so
+    the ranks' vectors concatenate to the whole graph's request_ranking_vector; gid is each trace's
+    global id -- its trace code on a graph of :func:`build_graph`, its index in the concatenation of
+    the ranks' traces on an uploaded shard."""
+    gid = np.empty(dg.T, np.int64)
+    r = np.empty(dg.T, np.float64)
+    dg.ctx.check(_lib.load().mr_graph_trace_rank_sharded(dg.h, ptr(r, C.c_double), ptr(gid, C.c_int64)),
+                 "mr_graph_trace_rank_sharded")
+    return gid, r
+
+
+def sharded_exemplars(dg, ops, m: int = 5) -> dict:
+    """For each op (node names or indices) the m traces of the WHOLE graph that matter most to the last
+    sharded ranking among the traces the op occurs in (mr_graph_exemplars_sharded; collective: every
+    rank calls it with the same ops and m): {op: [(global id, score), ...]}, score descending, global
+    id ascending on equal scores, identical on every rank.  Global ids as :func:`sharded_trace_rank`'s."""
+    from .graph import EX_MAX_OPS, check_exemplar_m, check_exemplar_ops
+
+    m = check_exemplar_m(m)
+    ops = check_exemplar_ops(ops)
+    idx = dg._node_indices(ops)
+    lib = _lib.load()
+    out = {}
+    for b in range(0, len(idx), EX_MAX_OPS):
+        part = np.asarray(idx[b:b + EX_MAX_OPS], np.int32)
+        k = int(part.size)
+        tr, sc, cnt = np.empty((k, m), np.int64), np.empty((k, m), np.float64), np.empty(k, np.int32)
+        dg.ctx.check(lib.mr_graph_exemplars_sharded(dg.h, ptr(part, C.c_int32), k, m, ptr(tr, C.c_int64),
+                                                    ptr(sc, C.c_double), ptr(cnt, C.c_int32)),
+                     "mr_graph_exemplars_sharded")
+        for i in range(k):
+            out[ops[b + i]] = [(int(t), np.float64(s)) for t, s in zip(tr[i, :cnt[i]], sc[i, :cnt[i]])]
+    return out
