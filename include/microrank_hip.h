@@ -524,6 +524,55 @@ int mr_windows_latency(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* sp
                        int32_t n_q, int method, double* out /*[n_windows * K * 2 * n_q]*/,
                        int64_t* count /*[n_windows * K * 2]*/, int32_t* status /*[n_windows]*/);
 
+/* ------------------------------------------------------------------ kind breakdown
+ * Which request shapes does the anomaly hit, and which pass through a suspect op unharmed?
+ * No reference counterpart: per asked pod-op of a window -- and for the window as a whole -- its
+ * trace kinds with their abnormal and normal trace counts.  "Every call path through the op is slow"
+ * points at the op; "one call path out of forty is" points at a caller.
+ * Window i = spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i] as in mr_windows_batch / mr_windows_latency;
+ * its partition is that window's mr_detect partition (state 0 outside or dropped, 1 normal, 2
+ * abnormal), computed on the device and never copied out.
+ * Kind of a trace: the table's exact class -- the sorted set of distinct pod-op codes over ALL rows of
+ * the trace and the bits of (float)(1.0 / rows of the trace) (pagerank.py:54-66's key).  A window
+ * keeps whole traces, so its kinds are the table's classes restricted to the traces of state 1 or 2; a
+ * kind is LIVE in the window when it has at least one such trace.
+ * Asked slots: podops[i * K + j], j < n_ops[i].  A pod-op code p >= 0 selects the live kinds whose op
+ * set contains p; -1 selects every live kind (the window's overall breakdown).  Per selected kind:
+ *   n_abn  its traces in state 2          n_nor  its traces in state 1
+ *   rep    its smallest trace code in state 2, or (n_abn == 0) its smallest trace code in state 1
+ *   spans  the rows of a member           ops    the distinct pod-ops of a member
+ * The answer of a slot is the first min(m, selected kinds) kinds under the total order n_abn
+ * descending, then n_nor ascending, then rep ascending (rep is unique per kind):
+ * kb_trace[(i * K + j) * m + e] = rep (-1 padded), kb_abn / kb_nor / kb_spans / kb_ops the same shape
+ * (0 padded), kb_n[i * K + j] the entries, kb_kinds[i * K + j] the number of selected kinds,
+ * kb_tot[(i * K + j) * 2 + {0, 1}] the summed n_abn / n_nor over ALL selected kinds -- for -1 the
+ * window's abnormal and normal trace counts, for an op its trace coverage on each side.  A slot
+ * asked twice is answered each time; an op with no trace in the window answers 0 entries and zero
+ * totals; entries j >= n_ops[i] are ignored and answer the padding.  status[i]: MR_OK, or
+ * MR_ERR_VALUE for an empty window (T2), whose outputs are the padding.  The answer does not depend
+ * on the cut into blocks, the chunking of the call's windows (their dense per-kind counters stay
+ * under a fixed scratch size), a window's place in the call, or the other windows: every count is an
+ * integer sum, every order total.  The ranking entries are untouched and no ranking state is read:
+ * evidence is a separate call that takes their top lists.
+ * MR_ERR_ARG: a null pointer, K outside 1..64, m outside 1..32 (the exemplar entries' limits),
+ * n_ops[i] outside 0..K, a code outside [-1, n_podops), a table of another context.
+ * MR_ERR_STATE: a trace shard of a larger table (cols.row set: its counts would cover this rank's
+ * traces only, and nothing merges the ranks'), a table without a per-trace index (its key bits did
+ * not fit), a table without trace-level times (per-span window times cut traces: the table's classes
+ * are not the window's kinds), or a table without a layout order (more than 4096 pod-ops, or past
+ * the edge / count limits of the window build); the message names which.  There is no fallback for
+ * any of them.
+ * An argument error leaves the context usable. */
+int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                              const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                              const int32_t* podops /*[n_windows * K], -1 = every kind*/, const int32_t* n_ops,
+                              int32_t K, int32_t m, int32_t* kb_trace /*[n_windows * K * m] rep trace code, -1 padded*/,
+                              int32_t* kb_abn, int32_t* kb_nor, int32_t* kb_spans,
+                              int32_t* kb_ops /*same shape, 0 padded*/, int32_t* kb_n /*[n_windows * K] entries*/,
+                              int32_t* kb_kinds /*[n_windows * K] selected kinds*/,
+                              int64_t* kb_tot /*[n_windows * K * 2] abnormal, normal traces*/,
+                              int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

@@ -135,6 +135,10 @@ SIGNATURES = {
     "mr_windows_latency": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, f64p, C.c_int32, C.c_int,
                                      f64p, i64p, i32p]),
+    # kind breakdown: many windows' trace kinds per asked pod-op (-1: every kind), with both sides' counts
+    "mr_windows_kind_breakdown": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, i32p, i32p, i32p,
+                                            i32p, i32p, i32p, i32p, i64p, i32p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "mr_comm_init": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),

@@ -34,17 +34,13 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "mr_exemplar_dev.h"   // the lists: order, insert, drain, merge (shared with mr_kind_breakdown.hip)
 #include "mr_iter_dev.h"
 #include "mr_prim.h"
 
-constexpr int EX_T = 256;          // threads per block (both kernels)
-constexpr int EX_MAXOPS = 64;      // asked ops per call
-constexpr int EX_MAXM = 32;        // traces per op
 constexpr int EX_HT = 256;         // slots of the asked ops' hash table (load <= 1/4)
 constexpr int EX_U = 4;            // ids per thread and round of k_ex_select
 constexpr int EX_Q = EX_T * EX_U;  // ids of a round: the most candidates a block queues between two drains
-constexpr int EX_LPT = 4;          // k_ex_merge: block lists per thread
-constexpr int EX_MAXB = EX_T * EX_LPT;   // most blocks of k_ex_select
 
 struct ExReq {
     int32_t n;
@@ -85,136 +81,6 @@ __global__ void __launch_bounds__(EX_T) k_trace_rank(const double* __restrict__ 
 }
 
 __device__ __forceinline__ uint32_t ex_hash(int32_t op) { return ((uint32_t)op * 2654435761u) >> 24; }
-// (s, t) ranks before (s2, t2): the larger score bits, then the smaller trace
-__device__ __forceinline__ bool ex_before(unsigned long long s, int32_t t, unsigned long long s2, int32_t t2) {
-    return s > s2 || (s == s2 && t < t2);
-}
-
-// One candidate into a sorted list held a lane per entry (m <= 32 < WAVE; ms / mt: this lane's entry,
-// c: the list's length): a ballot finds the place, a shuffle moves the tail up -- no chain of
-// dependent LDS accesses per candidate.  Wave-uniform arguments but ms / mt; true: the list changed.
-__device__ __forceinline__ bool ex_list_insert(unsigned long long& ms, int32_t& mt, int32_t& c, int32_t m, int lane,
-                                               unsigned long long s1, int32_t t1c) {
-    const bool valid = lane < c;
-    if (__ballot(valid && ms == s1 && mt == t1c)) return false;   // (an op listed twice in a row)
-    // the entries that stay ahead of the candidate: lanes [0, i)
-    const int32_t i = __popcll(__ballot(valid && !ex_before(s1, t1c, ms, mt)));
-    if (i >= m) return false;
-    const unsigned long long us = __shfl_up(ms, 1, WAVE);
-    const int32_t ut = __shfl_up(mt, 1, WAVE);
-    if (lane == i) {
-        ms = s1;
-        mt = t1c;
-    } else if (lane > i) {
-        ms = us;
-        mt = ut;
-    }
-    c = min(c + 1, m);
-    return true;
-}
-// The same into a list that holds ONE entry per trace kind (MR_EX_DISTINCT_KINDS; mk: this lane's kind
-// id, mx: the word that travels with it -- the kind id itself, or the position a window reads it by).
-// One more ballot finds the entry of the candidate's kind (at most one: the list is kind-distinct).
-// That entry at or ahead of the candidate's place: the candidate goes (an equal entry, the trace a
-// second time, included).  Behind it: the candidate takes its place, the entries between the two move
-// up one lane over the old entry, the length stays.  No such entry: the plain insert.  Candidates
-// come in atomicAdd order, so an equal-score member of a lower index may arrive after a higher one:
-// the replace runs on every graph.
-__device__ __forceinline__ bool ex_list_insert_kinds(unsigned long long& ms, int32_t& mt, int32_t& mk, int32_t& mx,
-                                                     int32_t& c, int32_t m, int lane, unsigned long long s1,
-                                                     int32_t t1c, int32_t k1, int32_t x1) {
-    const bool valid = lane < c;
-    const int32_t i = __popcll(__ballot(valid && !ex_before(s1, t1c, ms, mt)));
-    const unsigned long long same = __ballot(valid && mk == k1);
-    int32_t j = m;   // the last lane that moves up
-    if (same) {
-        j = __builtin_ctzll(same);
-        if (j < i) return false;
-    } else if (i >= m) {
-        return false;
-    }
-    const unsigned long long us = __shfl_up(ms, 1, WAVE);
-    const int32_t ut = __shfl_up(mt, 1, WAVE);
-    const int32_t uk = __shfl_up(mk, 1, WAVE);
-    const int32_t ux = __shfl_up(mx, 1, WAVE);
-    if (lane == i) {
-        ms = s1;
-        mt = t1c;
-        mk = k1;
-        mx = x1;
-    } else if (lane > i && lane <= j) {
-        ms = us;
-        mt = ut;
-        mk = uk;
-        mx = ux;
-    }
-    if (!same) c = min(c + 1, m);
-    return true;
-}
-// the drain of a block's queue (n candidates: score bits, trace, list) into its nu lists [u][m] in
-// LDS: a wave per list, entry j of the list in lane j; the wave reads 64 queue slots at a time and
-// inserts its own one by one.  Between two barriers of the caller; every thread of the block calls it.
-// DK (one entry per kind): qx / lx hold the word beside each candidate / entry; gk null: that word is
-// the kind id and qt the trace (k_ex_select); else it is a position, the kind id gk[x] and the trace
-// gt[x] (k_win_ex_select: both by position in global memory, read once per list and drain and once
-// per 64 candidates, so the queue and the lists keep the plain kernel's size but one word per entry).
-template <bool DK, class QU>
-__device__ __forceinline__ void ex_drain(int32_t n, int32_t nu, int32_t m, const unsigned long long* qs,
-                                         const int32_t* qt, const QU* qu, unsigned long long* ls, int32_t* lt,
-                                         int32_t* lc, const int32_t* qx = nullptr, int32_t* lx = nullptr,
-                                         const int32_t* __restrict__ gk = nullptr,
-                                         const int32_t* __restrict__ gt = nullptr) {
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1);
-    for (int32_t u = tid / WAVE; n > 0 && u < nu; u += EX_T / WAVE) {   // (wave-uniform)
-        int32_t c = lc[u];
-        unsigned long long ms = lane < c ? ls[u * m + lane] : 0ull;
-        int32_t mt = lane < c ? lt[u * m + lane] : -1;
-        int32_t mx = -1, mk = -1;
-        bool kinds_read = false;
-        if constexpr (DK) mx = lane < c ? lx[u * m + lane] : -1;
-        bool changed = false;
-        for (int32_t j0 = 0; j0 < n; j0 += WAVE) {
-            const int32_t j = j0 + lane;
-            const bool mine = j < n && (int32_t)qu[j] == u;
-            const unsigned long long cs = mine ? qs[j] : 0ull;
-            if constexpr (DK) {
-                unsigned long long pend = __ballot(mine);
-                if (!pend) continue;   // (uniform)
-                if (!kinds_read) {     // the entries' kinds, at the list's first candidate of this drain
-                    mk = gk ? (lane < c ? gk[mx] : -1) : mx;
-                    kinds_read = true;
-                }
-                const int32_t cx = mine ? qx[j] : -1;
-                const int32_t ck = gk ? (mine ? gk[cx] : -1) : cx;
-                const int32_t ct = mine ? (gt ? gt[cx] : qt[j]) : -1;
-                for (; pend; pend &= pend - 1) {
-                    const int src = __builtin_ctzll(pend);
-                    const unsigned long long s1 = __shfl(cs, src, WAVE);
-                    const int32_t t1c = __shfl(ct, src, WAVE);
-                    const int32_t k1 = __shfl(ck, src, WAVE);
-                    const int32_t x1 = __shfl(cx, src, WAVE);
-                    changed |= ex_list_insert_kinds(ms, mt, mk, mx, c, m, lane, s1, t1c, k1, x1);
-                }
-            } else {
-                const int32_t ct = mine ? qt[j] : -1;
-                for (unsigned long long pend = __ballot(mine); pend; pend &= pend - 1) {
-                    const int src = __builtin_ctzll(pend);
-                    const unsigned long long s1 = __shfl(cs, src, WAVE);
-                    const int32_t t1c = __shfl(ct, src, WAVE);
-                    changed |= ex_list_insert(ms, mt, c, m, lane, s1, t1c);
-                }
-            }
-        }
-        if (changed) {
-            if (lane < c) {
-                ls[u * m + lane] = ms;
-                lt[u * m + lane] = mt;
-                if constexpr (DK) lx[u * m + lane] = mx;
-            }
-            if (lane == 0) lc[u] = c;
-        }
-    }
-}
 
 // DK (MR_EX_DISTINCT_KINDS): the lists hold one trace per kind, krep[t] (the kind's first trace: the
 // kinds' own exact classes) beside every candidate and entry; the lists go out with their kind ids
@@ -328,117 +194,6 @@ __global__ void __launch_bounds__(EX_T) k_ex_select(const int64_t* __restrict__ 
     }
 }
 
-// a block merges list u of nb blocks' lists (ps / pt: [nb][nu][m]) into os / ot [nu * m] and on [nu]
-// DK (one entry per kind; pk / pm: the entries' kind ids and class sizes, om [nu * m] the answer's
-// sizes): every block's list is kind-distinct and sorted, a kind's best member lies in some block,
-// and if the kind is among the answer's m its best is in that block's list (fewer than m kinds rank
-// before it anywhere) -- so the answer is the merge with every later entry of an emitted kind
-// skipped, whatever the cut.  Still m rounds: a round emits the best head, and every thread moves
-// its heads of that kind on, past every kind emitted so far (ek, at most 32 words of LDS); popping
-// one head per round would take blocks * m rounds where the same kinds lead every block.
-template <bool DK>
-__device__ __forceinline__ void ex_merge_body(const unsigned long long* __restrict__ ps, const int32_t* __restrict__ pt,
-                                              int32_t nb, int32_t nu, int32_t m, int32_t u,
-                                              unsigned long long* __restrict__ os, int32_t* __restrict__ ot,
-                                              int32_t* __restrict__ on, const int32_t* __restrict__ pk = nullptr,
-                                              const int32_t* __restrict__ pm = nullptr,
-                                              int32_t* __restrict__ om = nullptr) {
-    __shared__ unsigned long long rs[EX_T / WAVE];
-    __shared__ int32_t rt[EX_T / WAVE];
-    __shared__ int32_t rk[DK ? EX_T / WAVE : 1], ek[DK ? EX_MAXM : 1];
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    // the heads of this thread's lists (list l = block l of k_ex_select; each is sorted, so the
-    // best of the heads is the next of the merge; a trace lies in one block: the winner names its list)
-    unsigned long long hs[EX_LPT];
-    int32_t ht[EX_LPT], hp[EX_LPT], hk[EX_LPT];
-#pragma unroll
-    for (int k = 0; k < EX_LPT; ++k) {
-        const int32_t l = tid + k * EX_T;
-        hp[k] = 0;
-        ht[k] = l < nb ? pt[((size_t)l * nu + u) * m] : -1;
-        hs[k] = l < nb ? ps[((size_t)l * nu + u) * m] : 0ull;
-        if constexpr (DK) hk[k] = l < nb ? pk[((size_t)l * nu + u) * m] : -1;
-    }
-    int32_t cnt = 0;
-    for (int32_t j = 0; j < m; ++j) {
-        unsigned long long bs = 0ull;
-        int32_t bt = -1, bk = -1;
-#pragma unroll
-        for (int k = 0; k < EX_LPT; ++k)
-            if (ht[k] >= 0 && (bt < 0 || ex_before(hs[k], ht[k], bs, bt))) {
-                bs = hs[k];
-                bt = ht[k];
-                if constexpr (DK) bk = hk[k];
-            }
-#pragma unroll
-        for (int d = WAVE / 2; d >= 1; d >>= 1) {
-            const unsigned long long s2 = __shfl_xor(bs, d, WAVE);
-            const int32_t t2 = __shfl_xor(bt, d, WAVE);
-            int32_t k2 = -1;
-            if constexpr (DK) k2 = __shfl_xor(bk, d, WAVE);
-            if (t2 >= 0 && (bt < 0 || ex_before(s2, t2, bs, bt))) {
-                bs = s2;
-                bt = t2;
-                if constexpr (DK) bk = k2;
-            }
-        }
-        __syncthreads();   // (the previous round's reads of rs / rt)
-        if (lane == 0) {
-            rs[wv] = bs;
-            rt[wv] = bt;
-            if constexpr (DK) rk[wv] = bk;
-        }
-        __syncthreads();
-        bs = rs[0];
-        bt = rt[0];
-        if constexpr (DK) bk = rk[0];
-        for (int w = 1; w < EX_T / WAVE; ++w)
-            if (rt[w] >= 0 && (bt < 0 || ex_before(rs[w], rt[w], bs, bt))) {
-                bs = rs[w];
-                bt = rt[w];
-                if constexpr (DK) bk = rk[w];
-            }
-        if (bt < 0) break;   // (uniform) every list is used up
-        if (tid == 0) {
-            os[(size_t)u * m + j] = bs;
-            ot[(size_t)u * m + j] = bt;
-        }
-        ++cnt;
-        if constexpr (DK) {
-            if (tid == 0) ek[j] = bk;
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < EX_LPT; ++k) {
-                if (ht[k] < 0 || hk[k] != bk) continue;
-                const size_t lb = ((size_t)(tid + k * EX_T) * nu + u) * m;
-                if (ht[k] == bt) om[(size_t)u * m + j] = pm[lb + hp[k]];   // (the winner's list: one thread)
-                for (bool seen = true; seen;) {   // the next entry of a kind not yet emitted
-                    ++hp[k];
-                    ht[k] = hp[k] < m ? pt[lb + hp[k]] : -1;
-                    hs[k] = hp[k] < m ? ps[lb + hp[k]] : 0ull;
-                    hk[k] = hp[k] < m ? pk[lb + hp[k]] : -1;
-                    seen = false;
-                    for (int32_t e = 0; ht[k] >= 0 && e <= j; ++e) seen |= ek[e] == hk[k];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < EX_LPT; ++k)
-                if (ht[k] == bt) {   // this list's head won: its next entry
-                    const int32_t l = tid + k * EX_T;
-                    ++hp[k];
-                    ht[k] = hp[k] < m ? pt[((size_t)l * nu + u) * m + hp[k]] : -1;
-                    hs[k] = hp[k] < m ? ps[((size_t)l * nu + u) * m + hp[k]] : 0ull;
-                }
-        }
-    }
-    for (int32_t j = cnt + tid; j < m; j += EX_T) {
-        os[(size_t)u * m + j] = 0ull;
-        ot[(size_t)u * m + j] = -1;
-        if constexpr (DK) om[(size_t)u * m + j] = 0;
-    }
-    if (tid == 0) on[u] = cnt;
-}
 // out: [nu * m] scores, [nu * m] traces, [nu] counts
 // (DK: the lists' kind ids pk and class sizes pm; om [nu * m] the class sizes)
 template <bool DK>

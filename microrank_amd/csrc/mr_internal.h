@@ -61,7 +61,8 @@ struct mr_ctx {
     // pinned error words of the PageRank groups a window batch has in flight (grown per call)
     int32_t* pin_flags = nullptr;
     size_t pin_flags_n = 0;
-    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars; grown per call)
+    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars) and of a kind
+    // breakdown chunk's (mr_windows_kind_breakdown); grown per call
     unsigned long long* pin_ex = nullptr;
     size_t pin_ex_n = 0;
     // one-shot peer all-reduce (mr_comm_peer_enable; mr_comm.hip): a receive region in uncached

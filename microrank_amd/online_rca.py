@@ -137,6 +137,34 @@ def _write_latency(top_list, score_list, rows, qv):
                     w.writerow([service, rank, side, int(row["n_" + side]), float(qj), float(v)])
 
 
+def _write_kinds(top_list, score_list, rows):
+    """kinds.csv beside result.csv: the whole window's block first (``result`` = ``*``), then for each op
+    of result.csv, in its order, the op's trace kinds in answer order (rows: window_kinds' dict)."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("kinds.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "trace", "n_abnormal", "n_normal", "spans", "ops"])
+        for label, key in [("*", None)] + [(service, service) for service, _ in ranked]:
+            if key not in rows:
+                continue
+            for rank, e in enumerate(rows[key][0], start=1):
+                w.writerow([label, rank, e[0], int(e[1]), int(e[2]), int(e[3]), int(e[4])])
+
+
+def _kind_m(m):
+    """The kind_breakdown keyword / windows_kind_breakdown's m: an integer in 1..32, else ValueError."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 32:
+        raise ValueError(f"the kinds per op must be an integer in 1..32, not {m!r}")
+    return int(m)
+
+
+def _kind_names(table, rows):
+    """windows_kind_breakdown's dict of one window with pod-op and trace names where the table has them."""
+    names, tnames = table.podop_names, table.trace_names
+    return {(None if c is None else names[c] if names is not None else c):
+            ([((tnames[e[0]] if tnames is not None else e[0]),) + e[1:] for e in r[0]],) + r[1:] for c, r in rows.items()}
+
+
 def _latency_args(q, what, method="linear"):
     """(q as a float64 vector, MR_LAT_* code, MR_Q_* code) of the latency keywords; ValueError for a bad
     q (get_operation_quantiles' rules, at most 16 values), what or method -- before any device work."""
@@ -192,13 +220,18 @@ def sweep_chain(plan):
 
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
-               latency_what="self"):
+               latency_what="self", kind_breakdown=None):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     latency (a q, scalar or sequence): ONE windows_latency call over the triggered windows' top lists;
-    its answer goes to plan["latency"] = (q, {m: windows_latency's dict}) for the replay (latency.csv)."""
+    its answer goes to plan["latency"] = (q, {m: windows_latency's dict}) for the replay (latency.csv).
+    kind_breakdown (an integer 1..32): ONE windows_kind_breakdown call over the triggered windows -- the
+    whole window, then its top list; plan["kinds"] = {m: windows_kind_breakdown's dict} (kinds.csv)."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     plan.pop("latency", None)
+    plan.pop("kinds", None)
+    if kind_breakdown is not None:
+        kind_breakdown = _kind_m(kind_breakdown)
     if latency is not None:
         qv = _latency_args(latency, latency_what)[0]
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
@@ -212,6 +245,9 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     if latency is not None:
         lat = windows_latency(plan["ctx"], wins, [r[0] for r in ranked], q=qv, what=latency_what)
         plan["latency"] = (qv, dict(zip(todo, lat)))
+    if kind_breakdown is not None:
+        kinds = windows_kind_breakdown(plan["ctx"], wins, [[None] + r[0].tolist() for r in ranked], m=kind_breakdown)
+        plan["kinds"] = dict(zip(todo, kinds))
     return dict(zip(todo, ranked))
 
 
@@ -236,13 +272,15 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
                       int(window_normal.value), int(window_abnormal.value))
 
 
-def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self"):
+def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self",
+               kind_breakdown=None):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
     _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds,
-                                         latency=latency, latency_what=latency_what), exemplar_kinds)
+                                         latency=latency, latency_what=latency_what, kind_breakdown=kind_breakdown),
+                exemplar_kinds)
 
 
 def _sweep_emit(plan, events, results, exemplar_kinds=False):
@@ -283,10 +321,12 @@ def _sweep_emit(plan, events, results, exemplar_kinds=False):
                                                              "n_normal": r[2], "n_abnormal": r[3]}
                     for c, r in lat[mm].items()}
             _write_latency(top_list, score_list, rows, qv)
+        if "kinds" in plan:     # (kind breakdown asked: the batch's answer, by name)
+            _write_kinds(top_list, score_list, _kind_names(plan["table"], plan["kinds"][mm]))
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
-                              exemplar_kinds=False, latency=None, latency_what="self"):
+                              exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -313,7 +353,19 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     per q; ``spans`` the op's rows on that side; value in the SLO's unit and rounding).  latency_what:
     "self" (a span's duration minus its children's: what separates a cause from its callers) or
     "duration".  On the sweep path from ONE windows_latency call over the triggered windows, window by
-    window from op_latency.  stdout and result.csv do not change; without it no file is written."""
+    window from op_latency.  stdout and result.csv do not change; without it no file is written.
+
+    kind_breakdown: an integer m (1..32): every trigger also rewrites ``kinds.csv`` beside result.csv
+    (columns result, rank, trace, n_abnormal, n_normal, spans, ops): which trace kinds (traces with the
+    same pod-ops and span count) the anomaly hits -- first the whole window's m kinds with the most
+    abnormal traces (``result`` = ``*``), then for each op of result.csv, in its order, the m such kinds
+    among those that pass through the op; ``trace`` names a trace of the kind to open, n_abnormal /
+    n_normal its traces on each side of the detector's partition, spans / ops a member's rows and
+    distinct pod-ops.  From ONE windows_kind_breakdown call over the triggered windows on the sweep
+    path, a call per window otherwise; tables whose window times vary within a trace are not covered
+    (the call raises).  stdout and result.csv do not change; without it no file is written."""
+    if kind_breakdown is not None:
+        kind_breakdown = _kind_m(kind_breakdown)
     check_converge_args(0.0, iters, 1)
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
@@ -326,12 +378,13 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what)
-    _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what)
+        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown)
+    _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what,
+                 kind_breakdown)
 
 
 def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False,
-                 latency=None, latency_what="self"):
+                 latency=None, latency_what="self", kind_breakdown=None):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -365,6 +418,8 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
             if latency is not None:
                 rows = op_latency(data, start_time, end_time, slo, top_list, q=latency, what=latency_what) if top_list else {}
                 _write_latency(top_list, score_list, rows, _latency_args(latency, latency_what)[0])
+            if kind_breakdown is not None:
+                _write_kinds(top_list, score_list, window_kinds(data, start_time, end_time, slo, top_list, m=kind_breakdown))
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -382,14 +437,16 @@ class RCAStream:
     (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars,
     exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger); latency, latency_what: its
-    keywords (latency.csv rewritten at every trigger)."""
+    keywords (latency.csv rewritten at every trigger); kind_breakdown: its keyword (kinds.csv rewritten
+    at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
-                 exemplar_kinds=False, latency=None, latency_what="self"):
+                 exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
         check_converge_args(0.0, iters, 1)
+        self.kind_breakdown = None if kind_breakdown is None else _kind_m(kind_breakdown)
         if latency is not None:
             _latency_args(latency, latency_what)
         self.latency, self.latency_what = latency, latency_what
@@ -463,14 +520,15 @@ class RCAStream:
                 data = self._frame()
                 if final:
                     self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
-                                            self.exemplar_kinds, self.latency, self.latency_what)
+                                            self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
                 events = sweep_chain(plan)
                 _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars,
                                                      exemplar_kinds=self.exemplar_kinds, latency=self.latency,
-                                                     latency_what=self.latency_what), self.exemplar_kinds)
+                                                     latency_what=self.latency_what,
+                                                     kind_breakdown=self.kind_breakdown), self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -487,7 +545,7 @@ class RCAStream:
         cur = self.cur
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
-                               self.exemplars, self.exemplar_kinds, self.latency, self.latency_what)
+                               self.exemplars, self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown)
             cur = nxt
         return cur
 
@@ -567,7 +625,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
-               exemplar_kinds=False, latency=None, latency_what="self"):
+               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -583,8 +641,13 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     distinct_kinds -- one trace per trace kind, as (traceID, score, traces of that kind).
 
     latency: a q (scalar or sequence) adds the key ``"latency"``: op_latency's dict for the ops of the
-    top list (latency_what: "self" or "duration").  Every other key stays what it is."""
+    top list (latency_what: "self" or "duration").  Every other key stays what it is.
+
+    kind_breakdown: an integer m (1..32) adds the key ``"kinds"``: window_kinds' dict for the whole
+    window (key None) and then the ops of the top list.  Every other key stays what it is."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if kind_breakdown is not None:
+        kind_breakdown = _kind_m(kind_breakdown)
     if latency is not None:
         _latency_args(latency, latency_what)
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
@@ -622,6 +685,9 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     if latency is not None:
         res["latency"] = op_latency(data, start_time, end_time, slo, res["top"], q=latency, what=latency_what, ctx=ctx,
                                     table=table, dev=dev) if m else {}
+    if kind_breakdown is not None:
+        res["kinds"] = window_kinds(data, start_time, end_time, slo, res["top"], m=kind_breakdown, ctx=ctx, table=table,
+                                    dev=dev)
     return res
 
 
@@ -726,6 +792,82 @@ def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="li
                                              ptr(status, C.c_int32)), "mr_windows_latency")
     return [{int(c): (out[i, j, 0].copy(), out[i, j, 1].copy(), int(cnt[i, j, 0]), int(cnt[i, j, 1]))
              for j, c in enumerate(ops[i])} for i in range(n)]
+
+
+def windows_kind_breakdown(ctx, windows, ops, *, m=8):
+    """Which trace kinds does each window's anomaly hit (mr_windows_kind_breakdown,
+    csrc/mr_kind_breakdown.hip)?  ``windows`` as rank_windows'; ``ops`` one sequence per window of
+    pod-op codes, None standing for "every kind" (the window's overall breakdown).  A kind is the
+    table's exact class of a trace: its set of pod-ops and its span count's fp32 reciprocal.  Returns
+    per window {code or None: (entries, n_kinds, n_abnormal, n_normal)}: ``entries`` the first m kinds
+    among the live kinds that contain the pod-op, as (trace code, n_abnormal, n_normal, spans, ops) --
+    most abnormal traces first, then fewest normal ones, then the smallest trace code; the trace is
+    the kind's first abnormal member (its first normal one where it has none), spans / ops a member's
+    rows and distinct pod-ops -- ``n_kinds`` the number of such kinds, ``n_abnormal`` / ``n_normal``
+    the traces of ALL of them on each side of the window's own detector partition.  An empty window
+    (rank_windows' status MR_ERR_VALUE) answers ([], 0, 0, 0).  ValueError for more than 64 ops in a
+    window, m outside 1..32 or len(ops) != len(windows); tables without trace-level times or without
+    a layout order are not covered (RuntimeError from the library)."""
+    m = _kind_m(m)
+    n = len(windows)
+    if len(ops) != n:
+        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
+    asked = [[None if o is None else int(o) for o in lst] for lst in ops]
+    k = max([len(a) for a in asked] + [1])
+    if k > 64:
+        raise ValueError(f"a window asks {k} ops; at most 64")
+    if n == 0:
+        return []
+    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
+           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
+    # (windows that share their SLO arrays give the library one pointer: one upload)
+    addr = {}
+    for i, w in enumerate(windows):
+        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
+            addr.setdefault(id(src), a.ctypes.data)
+    spans = (_lib.P * n)(*[w[0].h for w in windows])
+    t0 = np.array([int(w[1]) for w in windows], np.int64)
+    t1 = np.array([int(w[2]) for w in windows], np.int64)
+    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
+    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
+    cod = np.zeros((n, k), np.int32)
+    n_ops = np.array([len(a) for a in asked], np.int32)
+    for i, a in enumerate(asked):
+        cod[i, :len(a)] = [-1 if c is None else c for c in a]
+    col = [np.zeros((n, k, m), np.int32) for _ in range(5)]
+    cnt, kinds = np.zeros((n, k), np.int32), np.zeros((n, k), np.int32)
+    tot = np.zeros((n, k, 2), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_kind_breakdown(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                                    ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, m,
+                                                    *[ptr(c, C.c_int32) for c in col], ptr(cnt, C.c_int32),
+                                                    ptr(kinds, C.c_int32), ptr(tot, C.c_int64), ptr(status, C.c_int32)),
+              "mr_windows_kind_breakdown")
+    cols = [c.tolist() for c in col]
+    return [{c: (list(zip(*[cl[i][j][:cnt[i, j]] for cl in cols])), int(kinds[i, j]), int(tot[i, j, 0]), int(tot[i, j, 1]))
+             for j, c in enumerate(asked[i])} for i in range(n)]
+
+
+def window_kinds(data, start_time, end_time, slo, ops, *, m=8, ctx=None, table=None, dev=None):
+    """windows_kind_breakdown for one window by names: {None: the whole window, pod-op: ...} for the
+    pod-ops of ``ops`` (names, or codes), each (entries, n_kinds, n_abnormal, n_normal) with trace
+    names in the entries where the table has them.  An op that is no pod-op of the table raises
+    ValueError; ops past the call's 64 slots go in further calls."""
+    m = _kind_m(m)
+    ops = list(ops)
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    codes = _op_codes(table, ops)
+    a3, ok = slo_arrays(table, slo)
+    win = (dev, to_ns(start_time), to_ns(end_time), a3, ok)
+    asked = [None] + codes
+    rows = {}
+    for b in range(0, len(asked), 64):
+        rows.update(windows_kind_breakdown(ctx, [win], [asked[b:b + 64]], m=m)[0])
+    tnames = table.trace_names
+    return {key: ([((tnames[e[0]] if tnames is not None else e[0]),) + e[1:] for e in rows[c][0]],) + rows[c][1:]
+            for key, c in zip([None] + ops, asked)}
 
 
 def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):
