@@ -573,6 +573,69 @@ int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const mr_spans* co
                               int64_t* kb_tot /*[n_windows * K * 2] abnormal, normal traces*/,
                               int32_t* status /*[n_windows]*/);
 
+/* ------------------------------------------------------------------ call evidence
+ * Is a suspect op slow whoever calls it, or only from one caller -- and which of its downstream calls
+ * got slower on the abnormal traces?  No reference counterpart as an entry: the call graph of the
+ * reference's model (operation_operation, preprocess_data.py:156-163) shown per asked pod-op, on each
+ * side of the window's detector partition.
+ * Window i = spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i] as in mr_windows_batch; its partition is that
+ * window's mr_detect state (0 outside or dropped, 1 normal, 2 abnormal), computed on the device and never
+ * copied out.
+ * Call pair: (child row c, parent row r) with parent[c] >= 0 and span[r] == parent[c] -- T11's join, as in
+ * MR_LAT_SELF: traceID is ignored, EVERY row that shares the spanID code pairs with the child, an orphan
+ * makes no pair.
+ * Side: a pair belongs to side s (0 normal, 1 abnormal) when BOTH rows' traces have state s + 1 and both
+ * rows lie in the window (tstart >= t0 && tend <= t1, inclusive; t0 == INT64_MIN and t1 == INT64_MAX: the
+ * whole table, as in mr_op_latency).  With this rule the calls of edge (a -> b) on side s equal the
+ * multiplicity of b in operation_operation[a] that the reference builds from that side's trace list over
+ * the window's rows.
+ * Per edge (parent pod-op -> child pod-op) and side:
+ *   calls  the pair count (int64)
+ *   dsum   the sum of the CHILD row's duration over the pairs (int64 that wraps, as numpy's)
+ *   dmax   the largest child duration, 0 when calls == 0
+ * Asked slots: podops[i * K + j], j < n_ops[i], a pod-op code p.  Two directions per slot: direction 0,
+ * callers: the edges (q -> p), peer q; direction 1, callees: the edges (p -> c), peer c.  A self edge
+ * p -> p appears in both.  Only peers with calls[0] + calls[1] > 0 in the window are selected: an edge of
+ * the table that is dead in the window is not listed.
+ * The answer of a (slot, direction) is the first min(m, selected) peers under the total order abnormal
+ * calls descending, then normal calls ascending, then peer code ascending:
+ *   ce_peer[((i * K + j) * 2 + dir) * m + e]                             the peer's code, -1 padded
+ *   ce_calls / ce_dsum / ce_dmax[(((i * K + j) * 2 + dir) * m + e) * 2 + side]   0 padded
+ *   ce_n[(i * K + j) * 2 + dir]      the entries
+ *   ce_peers[(i * K + j) * 2 + dir]  the number of selected peers
+ *   ce_tot[((i * K + j) * 2 + dir) * 2 + side]  the calls summed over ALL selected peers, not only the listed
+ *   status[i]  MR_OK, or MR_ERR_VALUE for an empty window (T2), whose outputs are the padding
+ * A slot asked twice is answered each time; an op with no call in the window answers 0 entries and zero
+ * totals; entries j >= n_ops[i] answer the padding.
+ * Every count is an integer sum or maximum and every order is total, so the answer does not depend on
+ * the cut into blocks, the chunking of the call's windows (their dense per-edge counters stay under a
+ * fixed scratch size), a window's place in the call, or the other windows: it is bitwise reproducible.
+ * The ranking entries are untouched and no ranking state is read: evidence is a separate call that takes
+ * their top lists.  No layout order is needed: tables with more than 4096 pod-ops work.
+ * MR_ERR_ARG: a null pointer, K outside 1..64, m outside 1..32, n_ops[i] outside 0..K, a code outside
+ * [0, n_podops), a table of another context.
+ * MR_ERR_STATE: a trace shard of a larger table (cols.row set: parents may lie on another rank); a
+ * table without the per-trace index (its key bits did not fit, or it is empty), whose edge dictionary
+ * -- the sorted distinct (parent pod-op, child pod-op) keys of the join -- the counters and the
+ * selection are laid out by; a table without startTime / endTime columns (unlike mr_op_latency, whose
+ * caller brings the partition, this entry runs the window's detector, which reads them -- for the
+ * whole table too); a time window on a table without trace-level times (the entry tells "in the
+ * window" from the traces' states); a table whose join has 2^32 or more pairs in all (the selection
+ * orders by a key that packs both sides' counts in 32 bits each, exact below that) or 2^31 or more
+ * distinct edges (a list entry's id).  They are tested in this order and the message names which.
+ * There is no fallback for any of them.
+ * An argument error leaves the context usable. */
+int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                          const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                          const int32_t* podops /*[n_windows * K]*/, const int32_t* n_ops, int32_t K, int32_t m,
+                          int32_t* ce_peer /*[n_windows * K * 2 * m] peer code, -1 padded*/,
+                          int64_t* ce_calls, int64_t* ce_dsum,
+                          int64_t* ce_dmax /*[n_windows * K * 2 * m * 2]: ..., side; 0 padded*/,
+                          int32_t* ce_n /*[n_windows * K * 2] entries*/,
+                          int32_t* ce_peers /*[n_windows * K * 2] selected peers*/,
+                          int64_t* ce_tot /*[n_windows * K * 2 * 2] normal, abnormal calls*/,
+                          int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

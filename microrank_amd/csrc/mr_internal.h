@@ -61,8 +61,9 @@ struct mr_ctx {
     // pinned error words of the PageRank groups a window batch has in flight (grown per call)
     int32_t* pin_flags = nullptr;
     size_t pin_flags_n = 0;
-    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars) and of a kind
-    // breakdown chunk's (mr_windows_kind_breakdown); grown per call
+    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars), of a kind
+    // breakdown chunk's (mr_windows_kind_breakdown) and of a call-evidence chunk's (mr_windows_call_edges);
+    // grown per call
     unsigned long long* pin_ex = nullptr;
     size_t pin_ex_n = 0;
     // one-shot peer all-reduce (mr_comm_peer_enable; mr_comm.hip): a receive region in uncached
@@ -372,6 +373,7 @@ struct mr_spans {
     DBuf<long long> tmaxd, tts, tte;     // [NT] max duration, trace-level start / end
     int64_t n_po = 0, n_sv = 0, n_ed = 0, n_xj = 0;
     int64_t n_edge_keys = 0;             // distinct (parent op, child op) over the table: edge-set bound
+    int64_t n_join = 0;                  // (child row, parent row) pairs of T11's join over the table (mr_call_edges.hip's count bound)
     DBuf<uint64_t> ekey;                 // [n_edge_keys] those keys, ascending (parent << 32 | child)
     DBuf<int32_t> ed_eid, xj_eid;        // [n_ed], [n_xj] the dense edge id (index into ekey) of a key
     DBuf<int64_t> po_off;                // [NT+1] distinct pod-ops of a trace (code order) ...

@@ -644,6 +644,7 @@ int mr_spans_index(mr_ctx* ctx, mr_spans* s) {
         MR_TRY_HIP(ctx, hipStreamSynchronize(st));
         const int64_t J = h[0];
         s->n_xj = h[1];
+        s->n_join = h[0] + h[1];
         DBuf<uint64_t> ikey;
         MR_TRY(ikey.alloc(ctx, J));
         MR_TRY(s->xj_tc.alloc(ctx, s->n_xj));

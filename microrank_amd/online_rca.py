@@ -151,6 +151,40 @@ def _write_kinds(top_list, score_list, rows):
                 w.writerow([label, rank, e[0], int(e[1]), int(e[2]), int(e[3]), int(e[4])])
 
 
+def _write_calls(top_list, score_list, rows):
+    """calls.csv beside result.csv: for each op of result.csv, in its order, its callers and then its
+    callees in answer order (rows: window_calls' dict).  A mean is dsum / calls in float64 (0.0 for no
+    calls); means and maxima in the SLO's unit and rounding, as latency.csv's values."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("calls.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "direction", "peer", "calls_abnormal", "calls_normal", "mean_abnormal",
+                    "mean_normal", "max_abnormal", "max_normal"])
+        for service, _ in ranked:
+            if service not in rows:
+                continue
+            for direction, side in zip(("caller", "callee"), rows[service]):
+                for rank, e in enumerate(side[0], start=1):
+                    mean = [np.float64(e[3 + k]) / np.float64(e[1 + k]) if e[1 + k] else np.float64(0.0) for k in (0, 1)]
+                    w.writerow([service, rank, direction, e[0], int(e[1]), int(e[2])] +
+                               [float(x) for x in _latency_ms(mean)] + [float(x) for x in _latency_ms([e[5], e[6]])])
+
+
+def _call_m(m):
+    """The call_edges keyword / windows_call_edges' m: an integer in 1..32, else ValueError."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 32:
+        raise ValueError(f"the peers per op and direction must be an integer in 1..32, not {m!r}")
+    return int(m)
+
+
+def _call_names(table, rows):
+    """windows_call_edges' dict of one window with pod-op names (ops and peers) where the table has them."""
+    names = table.podop_names
+    if names is None:
+        return rows
+    return {names[c]: tuple(([(names[e[0]],) + e[1:] for e in side[0]],) + side[1:] for side in r) for c, r in rows.items()}
+
+
 def _kind_m(m):
     """The kind_breakdown keyword / windows_kind_breakdown's m: an integer in 1..32, else ValueError."""
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 32:
@@ -220,16 +254,21 @@ def sweep_chain(plan):
 
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
-               latency_what="self", kind_breakdown=None):
+               latency_what="self", kind_breakdown=None, call_edges=None):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     latency (a q, scalar or sequence): ONE windows_latency call over the triggered windows' top lists;
     its answer goes to plan["latency"] = (q, {m: windows_latency's dict}) for the replay (latency.csv).
     kind_breakdown (an integer 1..32): ONE windows_kind_breakdown call over the triggered windows -- the
-    whole window, then its top list; plan["kinds"] = {m: windows_kind_breakdown's dict} (kinds.csv)."""
+    whole window, then its top list; plan["kinds"] = {m: windows_kind_breakdown's dict} (kinds.csv).
+    call_edges (an integer 1..32): ONE windows_call_edges call over the triggered windows' top lists;
+    plan["calls"] = {m: windows_call_edges' dict} (calls.csv)."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     plan.pop("latency", None)
     plan.pop("kinds", None)
+    plan.pop("calls", None)
+    if call_edges is not None:
+        call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
         kind_breakdown = _kind_m(kind_breakdown)
     if latency is not None:
@@ -248,6 +287,9 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     if kind_breakdown is not None:
         kinds = windows_kind_breakdown(plan["ctx"], wins, [[None] + r[0].tolist() for r in ranked], m=kind_breakdown)
         plan["kinds"] = dict(zip(todo, kinds))
+    if call_edges is not None:
+        calls = windows_call_edges(plan["ctx"], wins, [r[0] for r in ranked], m=call_edges)
+        plan["calls"] = dict(zip(todo, calls))
     return dict(zip(todo, ranked))
 
 
@@ -273,13 +315,14 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
 
 
 def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self",
-               kind_breakdown=None):
+               kind_breakdown=None, call_edges=None):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
     _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds,
-                                         latency=latency, latency_what=latency_what, kind_breakdown=kind_breakdown),
+                                         latency=latency, latency_what=latency_what, kind_breakdown=kind_breakdown,
+                                         call_edges=call_edges),
                 exemplar_kinds)
 
 
@@ -323,10 +366,13 @@ def _sweep_emit(plan, events, results, exemplar_kinds=False):
             _write_latency(top_list, score_list, rows, qv)
         if "kinds" in plan:     # (kind breakdown asked: the batch's answer, by name)
             _write_kinds(top_list, score_list, _kind_names(plan["table"], plan["kinds"][mm]))
+        if "calls" in plan:     # (call evidence asked: the batch's answer, by name)
+            _write_calls(top_list, score_list, _call_names(plan["table"], plan["calls"][mm]))
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
-                              exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
+                              exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
+                              call_edges=None):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -363,7 +409,18 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     n_normal its traces on each side of the detector's partition, spans / ops a member's rows and
     distinct pod-ops.  From ONE windows_kind_breakdown call over the triggered windows on the sweep
     path, a call per window otherwise; tables whose window times vary within a trace are not covered
-    (the call raises).  stdout and result.csv do not change; without it no file is written."""
+    (the call raises).  stdout and result.csv do not change; without it no file is written.
+
+    call_edges: an integer m (1..32): every trigger also rewrites ``calls.csv`` beside result.csv
+    (columns result, rank, direction, peer, calls_abnormal, calls_normal, mean_abnormal, mean_normal,
+    max_abnormal, max_normal): for each op of result.csv, in its order, its m callers and then its m
+    callees with the most calls on the abnormal traces -- the calls of the edge on each side of the
+    detector's partition, and the mean and the largest duration of the called span (the SLO's unit and
+    rounding, as latency.csv; a mean of no calls is 0.0).  From ONE windows_call_edges call over the
+    triggered windows on the sweep path, a call per window otherwise.  stdout and result.csv do not
+    change; without it no file is written."""
+    if call_edges is not None:
+        call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
         kind_breakdown = _kind_m(kind_breakdown)
     check_converge_args(0.0, iters, 1)
@@ -378,13 +435,13 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown)
+        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown, call_edges)
     _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what,
-                 kind_breakdown)
+                 kind_breakdown, call_edges)
 
 
 def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False,
-                 latency=None, latency_what="self", kind_breakdown=None):
+                 latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -420,6 +477,8 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
                 _write_latency(top_list, score_list, rows, _latency_args(latency, latency_what)[0])
             if kind_breakdown is not None:
                 _write_kinds(top_list, score_list, window_kinds(data, start_time, end_time, slo, top_list, m=kind_breakdown))
+            if call_edges is not None:
+                _write_calls(top_list, score_list, window_calls(data, start_time, end_time, slo, top_list, m=call_edges))
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -438,14 +497,15 @@ class RCAStream:
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars,
     exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger); latency, latency_what: its
     keywords (latency.csv rewritten at every trigger); kind_breakdown: its keyword (kinds.csv rewritten
-    at every trigger)."""
+    at every trigger); call_edges: its keyword (calls.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
-                 exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
+                 exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
         check_converge_args(0.0, iters, 1)
+        self.call_edges = None if call_edges is None else _call_m(call_edges)
         self.kind_breakdown = None if kind_breakdown is None else _kind_m(kind_breakdown)
         if latency is not None:
             _latency_args(latency, latency_what)
@@ -520,7 +580,8 @@ class RCAStream:
                 data = self._frame()
                 if final:
                     self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
-                                            self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown)
+                                            self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
+                                            self.call_edges)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
@@ -528,7 +589,8 @@ class RCAStream:
                 _sweep_emit(plan, events, sweep_rank(plan, events, iters=self.iters, exemplars=self.exemplars,
                                                      exemplar_kinds=self.exemplar_kinds, latency=self.latency,
                                                      latency_what=self.latency_what,
-                                                     kind_breakdown=self.kind_breakdown), self.exemplar_kinds)
+                                                     kind_breakdown=self.kind_breakdown,
+                                                     call_edges=self.call_edges), self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -545,7 +607,8 @@ class RCAStream:
         cur = self.cur
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
-                               self.exemplars, self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown)
+                               self.exemplars, self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
+                               self.call_edges)
             cur = nxt
         return cur
 
@@ -625,7 +688,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
-               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None):
+               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -644,8 +707,13 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     top list (latency_what: "self" or "duration").  Every other key stays what it is.
 
     kind_breakdown: an integer m (1..32) adds the key ``"kinds"``: window_kinds' dict for the whole
-    window (key None) and then the ops of the top list.  Every other key stays what it is."""
+    window (key None) and then the ops of the top list.  Every other key stays what it is.
+
+    call_edges: an integer m (1..32) adds the key ``"calls"``: window_calls' dict for the ops of the top
+    list.  Every other key stays what it is."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if call_edges is not None:
+        call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
         kind_breakdown = _kind_m(kind_breakdown)
     if latency is not None:
@@ -687,6 +755,9 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
                                     table=table, dev=dev) if m else {}
     if kind_breakdown is not None:
         res["kinds"] = window_kinds(data, start_time, end_time, slo, res["top"], m=kind_breakdown, ctx=ctx, table=table,
+                                    dev=dev)
+    if call_edges is not None:
+        res["calls"] = window_calls(data, start_time, end_time, slo, res["top"], m=call_edges, ctx=ctx, table=table,
                                     dev=dev)
     return res
 
@@ -868,6 +939,88 @@ def window_kinds(data, start_time, end_time, slo, ops, *, m=8, ctx=None, table=N
     tnames = table.trace_names
     return {key: ([((tnames[e[0]] if tnames is not None else e[0]),) + e[1:] for e in rows[c][0]],) + rows[c][1:]
             for key, c in zip([None] + ops, asked)}
+
+
+def windows_call_edges(ctx, windows, ops, *, m=8):
+    """Who calls each window's suspect ops, and whom do they call (mr_windows_call_edges,
+    csrc/mr_call_edges.hip)?  ``windows`` as rank_windows'; ``ops`` one sequence of pod-op codes per
+    window -- the first element of rank_windows' tuples.  Returns per window {code: (callers, callees)},
+    each side (entries, n_peers, (calls_abnormal, calls_normal)): ``entries`` the first m peers among
+    those with a call in the window, as (peer code, calls_abn, calls_nor, dsum_abn, dsum_nor, dmax_abn,
+    dmax_nor) -- most abnormal calls first, then fewest normal ones, then the smallest peer code; a
+    call is a (child span, parent span) pair whose two traces lie on the same side of the window's own
+    detector partition, dsum / dmax the sum (int64, wrapping) and the maximum of the CHILD span's
+    duration in raw units -- ``n_peers`` the number of such peers and the totals the calls of ALL of
+    them.  An empty window (rank_windows' status MR_ERR_VALUE) answers ([], 0, (0, 0)) twice.
+    ValueError for more than 64 ops in a window, m outside 1..32 or len(ops) != len(windows); trace
+    shards and time windows on tables without trace-level times are not covered (RuntimeError from the
+    library)."""
+    m = _call_m(m)
+    n = len(windows)
+    if len(ops) != n:
+        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
+    asked = [[int(o) for o in lst] for lst in ops]
+    k = max([len(a) for a in asked] + [1])
+    if k > 64:
+        raise ValueError(f"a window asks {k} ops; at most 64")
+    if n == 0:
+        return []
+    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
+           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
+    # (windows that share their SLO arrays give the library one pointer: one upload)
+    addr = {}
+    for i, w in enumerate(windows):
+        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
+            addr.setdefault(id(src), a.ctypes.data)
+    spans = (_lib.P * n)(*[w[0].h for w in windows])
+    t0 = np.array([int(w[1]) for w in windows], np.int64)
+    t1 = np.array([int(w[2]) for w in windows], np.int64)
+    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
+    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
+    cod = np.zeros((n, k), np.int32)
+    n_ops = np.array([len(a) for a in asked], np.int32)
+    for i, a in enumerate(asked):
+        cod[i, :len(a)] = a
+    peer = np.zeros((n, k, 2, m), np.int32)
+    calls, dsum, dmax = (np.zeros((n, k, 2, m, 2), np.int64) for _ in range(3))
+    cnt, peers = np.zeros((n, k, 2), np.int32), np.zeros((n, k, 2), np.int32)
+    tot = np.zeros((n, k, 2, 2), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_call_edges(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                                ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, m, ptr(peer, C.c_int32),
+                                                ptr(calls, C.c_int64), ptr(dsum, C.c_int64), ptr(dmax, C.c_int64),
+                                                ptr(cnt, C.c_int32), ptr(peers, C.c_int32), ptr(tot, C.c_int64),
+                                                ptr(status, C.c_int32)), "mr_windows_call_edges")
+    pl, cl, sl, xl = peer.tolist(), calls.tolist(), dsum.tolist(), dmax.tolist()
+
+    def side(i, j, d):
+        ent = [(pl[i][j][d][e], cl[i][j][d][e][1], cl[i][j][d][e][0], sl[i][j][d][e][1], sl[i][j][d][e][0],
+                xl[i][j][d][e][1], xl[i][j][d][e][0]) for e in range(cnt[i, j, d])]
+        return ent, int(peers[i, j, d]), (int(tot[i, j, d, 1]), int(tot[i, j, d, 0]))
+
+    return [{c: (side(i, j, 0), side(i, j, 1)) for j, c in enumerate(asked[i])} for i in range(n)]
+
+
+def window_calls(data, start_time, end_time, slo, ops, *, m=8, ctx=None, table=None, dev=None):
+    """windows_call_edges for one window by names: {pod-op: (callers, callees)} for the pod-ops of
+    ``ops`` (names, or codes), peers by name where the table has names.  An op that is no pod-op of
+    the table raises ValueError; ops past the call's 64 slots go in further calls."""
+    m = _call_m(m)
+    ops = list(ops)
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    codes = _op_codes(table, ops)
+    if not ops:
+        return {}
+    a3, ok = slo_arrays(table, slo)
+    win = (dev, to_ns(start_time), to_ns(end_time), a3, ok)
+    rows = {}
+    for b in range(0, len(codes), 64):
+        rows.update(windows_call_edges(ctx, [win], [codes[b:b + 64]], m=m)[0])
+    names = table.podop_names
+    pn = (lambda c: names[c]) if names is not None else (lambda c: c)
+    return {key: tuple(([(pn(e[0]),) + e[1:] for e in sd[0]],) + sd[1:] for sd in rows[c]) for key, c in zip(ops, codes)}
 
 
 def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):

@@ -1,0 +1,121 @@
+"""What the call evidence costs on one MI355X (DESIGN §3 "Call evidence").
+
+The C2 bench tables: bench.c2_window_stream(N, 1000, 200_000, rank=0), N = 256 distinct windows of one
+system, each its own span table resident in HBM, the SLO of the normal period from mr_slo -- the windows
+of bench.py's default line.  After a warm-up, medians of CALLS calls, each bracketed by HIP events on the
+context stream and by the host's clock (every call ends in a read-back: the host time is what a caller
+waits for):
+
+  (a) one ranking step: rank_windows over the N windows (one mr_windows_batch_ex call);
+  (b) one windows_kind_breakdown call over the N windows: the whole window plus each top list, m = 8;
+  (c) one windows_call_edges call over the N windows: each top list, m = 8;
+  (d) mr_copy_peak, and the bytes the count pass of (c) reads per window under the assumption that every
+      trace is in the window's partition (a C2 window spans its table): 5 B per row (its trace code and
+      that trace's state byte) and, for a row with a parent, 49 B more -- parent 8, id_off 16, duration 8,
+      pod-op 4, id_rows 4, the parent row's trace 4, state 1 and pod-op 4 (the binary search in the edge
+      dictionary stays in cache and is not counted).
+
+The GPU work runs in one child process under `timeout`; the parent never opens the GPU.
+
+    python3 scripts/call_edges_cost.py [--windows 256] [--out profiles/call_edges.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
+    sys.path.insert(0, p)
+
+from converge_cost import Events  # noqa: E402  (scripts/ is sys.path[0])
+
+CALLS, WARMUP, M = 7, 2, 8
+
+
+def summary(v):
+    return {"event_ms_median": statistics.median(m for m, _ in v), "event_ms_min": min(m for m, _ in v),
+            "event_ms_max": max(m for m, _ in v), "host_ms_median": statistics.median(w for _, w in v)}
+
+
+def child(a):
+    import ctypes as C
+
+    import bench
+    from microrank_amd import _lib
+    from microrank_amd.online_rca import rank_windows, windows_call_edges, windows_kind_breakdown
+    from microrank_amd.preprocess_data import DeviceSpans
+
+    tabs = bench.c2_window_stream(a.windows, a.ops, a.traces, 0)   # (the generators fork before the GPU is touched)
+    lib = _lib.load()
+    ctx = _lib.default_context()
+    a3, ok = bench.slo_from_gpu(ctx, next(tabs))
+    wins, rows, with_parent = [], [], []
+    for t in tabs:
+        t0 = int(t.tstart.min())
+        rows.append(int(t.n_spans))
+        with_parent.append(int((t.parent >= 0).sum()))
+        d = DeviceSpans(ctx, t)
+        d.table = None   # (the host columns are slab views the next tables overwrite)
+        wins.append((d, t0, t0 + 5 * 60 * 10**9, a3, ok))
+    ev = Events(lib.mr_ctx_stream(ctx.h))
+    res = {"windows": len(wins), "ops": a.ops, "traces": a.traces, "calls": CALLS, "warmup": WARMUP, "m": M,
+           "rows_per_window": [min(rows), statistics.median(rows), max(rows)]}
+
+    def timed(fn):
+        t = []
+        for r in range(WARMUP + CALLS):
+            x = ev.time_ms(fn)
+            if r >= WARMUP:
+                t.append(x)
+        return summary(t)
+
+    keep = {}
+    res["ranking_step"] = timed(lambda: keep.__setitem__("r", rank_windows(ctx, wins)))
+    tops = [r[0] for r in keep["r"]]
+    res["asked_per_window"] = [min(len(t) for t in tops), max(len(t) for t in tops)]
+    res["kind_breakdown"] = timed(lambda: windows_kind_breakdown(ctx, wins, [[None] + t.tolist() for t in tops], m=M))
+    res["call_edges"] = timed(lambda: keep.__setitem__("c", windows_call_edges(ctx, wins, tops, m=M)))
+    listed = [sum(len(side[0]) for v in w.values() for side in v) for w in keep["c"]]
+    res["listed_edges_per_window"] = [min(listed), max(listed)]
+    res["calls_per_window_abn_nor"] = [[sum(v[1][2][k] for v in w.values()) for k in (0, 1)] for w in keep["c"][:4]]
+    g = C.c_double()
+    ctx.check(lib.mr_copy_peak(ctx.h, 1 << 30, 5, C.byref(g)), "mr_copy_peak")
+    res["copy_peak_gbs"] = g.value
+    byt = [5 * s + 49 * p for s, p in zip(rows, with_parent)]
+    res["count_pass_bytes_per_window"] = [min(byt), statistics.median(byt), max(byt)]
+    res["count_pass_bytes_per_call"] = sum(byt)
+    res["call_fraction_of_copy_peak"] = sum(byt) / (res["call_edges"]["event_ms_median"] * 1e-3) / (g.value * 1e9)
+    for w in wins:
+        w[0].close()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=256)
+    ap.add_argument("--ops", type=int, default=1000)
+    ap.add_argument("--traces", type=int, default=200_000)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "call_edges.json"))
+    ap.add_argument("--step-timeout", type=int, default=840)
+    ap.add_argument("--child", action="store_true")
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child",
+           "--windows", str(a.windows), "--ops", str(a.ops), "--traces", str(a.traces)]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        sys.exit(f"the GPU step failed (exit status {p.returncode})")
+    res = json.loads(line[-1][len("RESULT "):])
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
