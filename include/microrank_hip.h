@@ -636,6 +636,63 @@ int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_spans* const*
                           int64_t* ce_tot /*[n_windows * K * 2 * 2] normal, abnormal calls*/,
                           int32_t* status /*[n_windows]*/);
 
+/* ------------------------------------------------------------------ timeline evidence
+ * WHEN inside the window: did the anomaly start at 14:03:10 and is it still going on, or was it a burst of
+ * twenty seconds that is over; did the suspect op get slow at the moment the abnormal traces began, or was
+ * it slow all along; is the abnormal share rising or falling?  No reference counterpart: per asked pod-op --
+ * and for the window as a whole -- a dense, exact, integer histogram over time buckets, on each side of the
+ * window's detector partition.  Every other evidence entry collapses the window's time axis.
+ * Window i = spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i]; its partition and its sides are exactly those of
+ * mr_windows_call_edges / mr_windows_latency: that window's mr_detect state (0 outside or dropped, 1 normal,
+ * 2 abnormal), computed on the device and never copied out; side 0 is normal, side 1 abnormal; t0 ==
+ * INT64_MIN and t1 == INT64_MAX: the whole table.
+ * Asked slots: podops[i * K + j], j < n_ops[i].
+ *   A pod-op code p >= 0: the selected rows of (p, side) are mr_op_latency's -- podop[r] == p, the row's trace
+ *   in state side + 1, the row inside the window.  A row's value is duration[r] for MR_LAT_DURATION and
+ *   duration[r] - csum[span[r]] for MR_LAT_SELF, csum as in mr_op_latency (T11's join: traceID ignored; the
+ *   buffer the first MR_LAT_SELF call on the table computes and keeps); int64 arithmetic that wraps, and the
+ *   value may be negative.
+ *   -1: the window's own timeline.  Each trace of state 1 or 2 counts ONCE, through the per-trace index; its
+ *   value is the trace's tend - tstart (int64 that wraps), whatever `what` is.
+ * Bucket of a row or trace: from its TRACE-LEVEL tstart (the table's times are constant within a trace, so a
+ * trace falls in one bucket).  tstart < b0[i]: "before".  Otherwise delta = (uint64)tstart - (uint64)b0[i]
+ * (exact since tstart >= b0, for b0 == INT64_MIN too), b = delta / bw[i] (unsigned); b >= B: "after".
+ * Outputs, window i, asked entry j:
+ *   tl_cnt / tl_sum / tl_max[((i * K + j) * B + b) * 2 + side]  the selected rows (traces) of bucket b: their
+ *       number, the sum of their values (int64 that wraps, as numpy's) and the largest value; tl_max is 0
+ *       where tl_cnt is 0
+ *   tl_out[((i * K + j) * 2 + side) * 2 + {0, 1}]  the selected rows that fell before / after the bucket range
+ *   status[i]  MR_OK, or MR_ERR_VALUE for an empty window (T2), whose outputs are all zero
+ * So for an op slot the buckets' tl_cnt + before + after equals mr_windows_latency's count of that op and
+ * side, and for slot -1 the window's normal or abnormal trace count.  A slot asked twice is answered each
+ * time; an op without a row in the window answers zeros; entries j >= n_ops[i] answer zeros.
+ * Every output is an integer sum or maximum, so the answer does not depend on the cut into blocks, the
+ * chunking of the call's windows (their dense counters, K * (B + 2) * 2 * 3 words per window, stay under a
+ * fixed scratch size), a window's place in the call, or the other windows: it is bitwise reproducible.
+ * One row pass and one trace pass answer a chunk of windows, never a launch per op or per bucket.  The
+ * ranking entries are untouched and no ranking state is read: evidence is a separate call that takes their
+ * top lists.
+ * MR_ERR_ARG: a null pointer, K outside 1..64, B outside 1..512, bw[i] <= 0, n_ops[i] outside 0..K, a code
+ * outside [-1, n_podops), an unknown what, a table of another context.
+ * MR_ERR_STATE, tested in this order: a table without startTime / endTime columns; a table whose times are
+ * not trace-level (per-span window times: a trace must fall in one bucket -- for the whole table too; an
+ * unindexed table with rows has no record that they are); MR_LAT_SELF on a trace shard of a larger table
+ * (cols.row set: children may lie on another rank); slot -1 on a trace shard (its counts would cover this
+ * rank's traces only), or on a table without the per-trace index.  The message names which.  There is no
+ * fallback for any of them.  Op slots with MR_LAT_DURATION on a shard are allowed: they cover THAT RANK's
+ * rows, under that rank's detector partition; nothing merges the ranks' timelines.
+ * An argument error leaves the context usable. */
+int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                        const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                        const int32_t* podops /*[n_windows * K], -1 = the window's traces*/, const int32_t* n_ops,
+                        int32_t K, int what /*MR_LAT_DURATION | MR_LAT_SELF*/,
+                        const int64_t* b0 /*[n_windows] bucket origin, ns*/,
+                        const int64_t* bw /*[n_windows] bucket width, ns, > 0*/, int32_t B /*buckets, 1..512*/,
+                        int64_t* tl_cnt, int64_t* tl_sum,
+                        int64_t* tl_max /*[n_windows * K * B * 2]: window, slot, bucket, side*/,
+                        int64_t* tl_out /*[n_windows * K * 2 * 2]: window, slot, side, {before, after}*/,
+                        int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

@@ -143,6 +143,10 @@ SIGNATURES = {
     "mr_windows_call_edges": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, i32p, i64p, i64p, i64p,
                                         i32p, i32p, i64p, i32p]),
+    # timeline evidence: many windows' per-bucket counts, sums and maxima per asked pod-op (-1: the window's traces)
+    "mr_windows_timeline": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, i64p, i64p, C.c_int32, i64p,
+                                      i64p, i64p, i64p, i32p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "mr_comm_init": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),

@@ -430,6 +430,9 @@ struct mr_spans {
 };
 
 int mr_spans_index(mr_ctx* ctx, mr_spans* s);
+// mr_latency.hip: s->csum computed on first use (stream-ordered) and kept with the table; mr_timeline.hip's
+// MR_LAT_SELF reads the same buffer
+int lat_csum_ensure(mr_ctx* ctx, const mr_spans* s);
 
 // Handles given out across the ABI (graphs, span tables) are registered with their context:
 // mr_ctx_destroy frees the ones still live, and freeing a handle that is not registered (its

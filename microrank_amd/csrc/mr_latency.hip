@@ -208,6 +208,9 @@ struct LatReq {
     int32_t n_ops;
 };
 
+}  // namespace
+
+// (mr_internal.h: mr_timeline.hip's MR_LAT_SELF reads the same buffer)
 int lat_csum_ensure(mr_ctx* ctx, const mr_spans* s) {
     if (s->csum_ok) return MR_OK;
     MR_TRY(s->csum.zero(ctx, (size_t)std::max<int64_t>(s->n_span_codes, 1)));
@@ -218,6 +221,8 @@ int lat_csum_ensure(mr_ctx* ctx, const mr_spans* s) {
     s->csum_ok = true;   // (stream-ordered: every reader is enqueued behind it on the context's stream)
     return MR_OK;
 }
+
+namespace {
 
 // the arguments both entries share
 int lat_args(mr_ctx* ctx, const char* who, int what, const double* q, int32_t n_q, int method) {

@@ -170,6 +170,49 @@ def _write_calls(top_list, score_list, rows):
                                [float(x) for x in _latency_ms(mean)] + [float(x) for x in _latency_ms([e[5], e[6]])])
 
 
+def _write_timeline(top_list, score_list, rows):
+    """timeline.csv beside result.csv: the window's own block first (``result`` = ``*``, rank 0), then for
+    each op of result.csv, in its order, one row per time bucket (rows: window_timeline's dict): the
+    bucket's first ns, the rows (for ``*``: traces) that start in it on each side of the detector's
+    partition, and the mean and the largest of their values.  A mean is sum / count in float64 (0.0 for
+    no rows); means and maxima in the SLO's unit and rounding, as calls.csv's."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("timeline.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "bucket", "start", "count_abnormal", "count_normal", "mean_abnormal", "mean_normal",
+                    "max_abnormal", "max_normal"])
+        for rank, (label, key) in enumerate([("*", -1)] + [(service, service) for service, _ in ranked]):
+            r = rows.get(key)
+            if r is None:
+                continue
+            for b, (start, cnt, tot, mx) in enumerate(zip(r["start"], r["cnt"], r["sum"], r["max"])):
+                mean = [np.float64(tot[k]) / np.float64(cnt[k]) if cnt[k] else np.float64(0.0) for k in (1, 0)]
+                w.writerow([label, rank, b, int(start), int(cnt[1]), int(cnt[0])] + [float(x) for x in _latency_ms(mean)] +
+                           [float(x) for x in _latency_ms([mx[1], mx[0]])])
+
+
+def _timeline_args(buckets, what="self"):
+    """(buckets, MR_LAT_* code) of the timeline keywords: buckets an integer in 1..512, what "self" or
+    "duration"; ValueError otherwise -- before any device work."""
+    if isinstance(buckets, bool) or not isinstance(buckets, (int, np.integer)) or not 1 <= buckets <= 512:
+        raise ValueError(f"the time buckets must be an integer in 1..512, not {buckets!r}")
+    w = _lib.LATENCY_VALUES.get(what) if isinstance(what, str) else None
+    if w is None:
+        raise ValueError(f"what must be one of {sorted(_lib.LATENCY_VALUES)}, not {what!r}")
+    return int(buckets), w
+
+
+def _timeline_lists(r):
+    """A slot of windows_timeline's answer as plain lists of Python ints."""
+    return {k: v.tolist() for k, v in r.items()}
+
+
+def _timeline_names(table, rows):
+    """windows_timeline's dict of one window with pod-op names where the table has them (-1 stays -1)."""
+    names = table.podop_names
+    return {(c if c < 0 or names is None else names[c]): _timeline_lists(r) for c, r in rows.items()}
+
+
 def _call_m(m):
     """The call_edges keyword / windows_call_edges' m: an integer in 1..32, else ValueError."""
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 32:
@@ -254,7 +297,7 @@ def sweep_chain(plan):
 
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
-               latency_what="self", kind_breakdown=None, call_edges=None):
+               latency_what="self", kind_breakdown=None, call_edges=None, timeline=None):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     latency (a q, scalar or sequence): ONE windows_latency call over the triggered windows' top lists;
@@ -262,11 +305,17 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     kind_breakdown (an integer 1..32): ONE windows_kind_breakdown call over the triggered windows -- the
     whole window, then its top list; plan["kinds"] = {m: windows_kind_breakdown's dict} (kinds.csv).
     call_edges (an integer 1..32): ONE windows_call_edges call over the triggered windows' top lists;
-    plan["calls"] = {m: windows_call_edges' dict} (calls.csv)."""
+    plan["calls"] = {m: windows_call_edges' dict} (calls.csv).
+    timeline (an integer 1..512, the buckets): ONE windows_timeline call over the triggered windows -- the
+    window's own traces (-1), then its top list; plan["timeline"] = {m: windows_timeline's dict}
+    (timeline.csv)."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     plan.pop("latency", None)
     plan.pop("kinds", None)
     plan.pop("calls", None)
+    plan.pop("timeline", None)
+    if timeline is not None:
+        timeline = _timeline_args(timeline)[0]
     if call_edges is not None:
         call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
@@ -290,6 +339,9 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     if call_edges is not None:
         calls = windows_call_edges(plan["ctx"], wins, [r[0] for r in ranked], m=call_edges)
         plan["calls"] = dict(zip(todo, calls))
+    if timeline is not None:
+        tl = windows_timeline(plan["ctx"], wins, [[-1] + r[0].tolist() for r in ranked], buckets=timeline)
+        plan["timeline"] = dict(zip(todo, tl))
     return dict(zip(todo, ranked))
 
 
@@ -315,14 +367,14 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
 
 
 def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self",
-               kind_breakdown=None, call_edges=None):
+               kind_breakdown=None, call_edges=None, timeline=None):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
     _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds,
                                          latency=latency, latency_what=latency_what, kind_breakdown=kind_breakdown,
-                                         call_edges=call_edges),
+                                         call_edges=call_edges, timeline=timeline),
                 exemplar_kinds)
 
 
@@ -368,11 +420,13 @@ def _sweep_emit(plan, events, results, exemplar_kinds=False):
             _write_kinds(top_list, score_list, _kind_names(plan["table"], plan["kinds"][mm]))
         if "calls" in plan:     # (call evidence asked: the batch's answer, by name)
             _write_calls(top_list, score_list, _call_names(plan["table"], plan["calls"][mm]))
+        if "timeline" in plan:  # (timeline asked: the batch's answer, by name)
+            _write_timeline(top_list, score_list, _timeline_names(plan["table"], plan["timeline"][mm]))
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
                               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                              call_edges=None):
+                              call_edges=None, timeline=None):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -418,7 +472,20 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     detector's partition, and the mean and the largest duration of the called span (the SLO's unit and
     rounding, as latency.csv; a mean of no calls is 0.0).  From ONE windows_call_edges call over the
     triggered windows on the sweep path, a call per window otherwise.  stdout and result.csv do not
-    change; without it no file is written."""
+    change; without it no file is written.
+
+    timeline: an integer B (1..512): every trigger also rewrites ``timeline.csv`` beside result.csv
+    (columns result, rank, bucket, start, count_abnormal, count_normal, mean_abnormal, mean_normal,
+    max_abnormal, max_normal): the window cut into B time buckets by trace start (``start`` the bucket's
+    first ns) -- first the window's own traces (``result`` = ``*``, rank 0: how many normal and abnormal
+    traces start in the bucket, the mean and the largest endTime - startTime), then for each op of
+    result.csv, in its order, the op's spans on each side of the detector's partition with the mean and
+    the largest self time (the SLO's unit and rounding, as calls.csv; a mean of no rows is 0.0).  From
+    ONE windows_timeline call over the triggered windows on the sweep path, a call per window otherwise;
+    tables whose window times vary within a trace are not covered (the call raises).  stdout and
+    result.csv do not change; without it no file is written."""
+    if timeline is not None:
+        timeline = _timeline_args(timeline)[0]
     if call_edges is not None:
         call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
@@ -435,13 +502,14 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     end = data["endTime"].max()
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
-        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown, call_edges)
+        return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown, call_edges,
+                          timeline)
     _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what,
-                 kind_breakdown, call_edges)
+                 kind_breakdown, call_edges, timeline)
 
 
 def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False,
-                 latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
+                 latency=None, latency_what="self", kind_breakdown=None, call_edges=None, timeline=None):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -479,6 +547,9 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
                 _write_kinds(top_list, score_list, window_kinds(data, start_time, end_time, slo, top_list, m=kind_breakdown))
             if call_edges is not None:
                 _write_calls(top_list, score_list, window_calls(data, start_time, end_time, slo, top_list, m=call_edges))
+            if timeline is not None:
+                _write_timeline(top_list, score_list,
+                                window_timeline(data, start_time, end_time, slo, top_list, buckets=timeline))
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -497,14 +568,17 @@ class RCAStream:
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's; exemplars,
     exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger); latency, latency_what: its
     keywords (latency.csv rewritten at every trigger); kind_breakdown: its keyword (kinds.csv rewritten
-    at every trigger); call_edges: its keyword (calls.csv rewritten at every trigger)."""
+    at every trigger); call_edges: its keyword (calls.csv rewritten at every trigger); timeline: its keyword
+    (timeline.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
-                 exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
+                 exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
+                 timeline=None):
         check_converge_args(0.0, iters, 1)
+        self.timeline = None if timeline is None else _timeline_args(timeline)[0]
         self.call_edges = None if call_edges is None else _call_m(call_edges)
         self.kind_breakdown = None if kind_breakdown is None else _kind_m(kind_breakdown)
         if latency is not None:
@@ -581,7 +655,7 @@ class RCAStream:
                 if final:
                     self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
                                             self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
-                                            self.call_edges)
+                                            self.call_edges, self.timeline)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
@@ -590,7 +664,8 @@ class RCAStream:
                                                      exemplar_kinds=self.exemplar_kinds, latency=self.latency,
                                                      latency_what=self.latency_what,
                                                      kind_breakdown=self.kind_breakdown,
-                                                     call_edges=self.call_edges), self.exemplar_kinds)
+                                                     call_edges=self.call_edges, timeline=self.timeline),
+                            self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
             self.dead = True
@@ -608,7 +683,7 @@ class RCAStream:
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
                                self.exemplars, self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
-                               self.call_edges)
+                               self.call_edges, self.timeline)
             cur = nxt
         return cur
 
@@ -688,7 +763,8 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
-               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None):
+               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
+               timeline=None):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -710,8 +786,13 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     window (key None) and then the ops of the top list.  Every other key stays what it is.
 
     call_edges: an integer m (1..32) adds the key ``"calls"``: window_calls' dict for the ops of the top
-    list.  Every other key stays what it is."""
+    list.  Every other key stays what it is.
+
+    timeline: an integer B (1..512) adds the key ``"timeline"``: window_timeline's dict for the window's
+    own traces (key -1) and then the ops of the top list, over B buckets.  Every other key stays what it is."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if timeline is not None:
+        timeline = _timeline_args(timeline)[0]
     if call_edges is not None:
         call_edges = _call_m(call_edges)
     if kind_breakdown is not None:
@@ -759,6 +840,9 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     if call_edges is not None:
         res["calls"] = window_calls(data, start_time, end_time, slo, res["top"], m=call_edges, ctx=ctx, table=table,
                                     dev=dev)
+    if timeline is not None:
+        res["timeline"] = window_timeline(data, start_time, end_time, slo, res["top"], buckets=timeline, ctx=ctx,
+                                          table=table, dev=dev)
     return res
 
 
@@ -1021,6 +1105,103 @@ def window_calls(data, start_time, end_time, slo, ops, *, m=8, ctx=None, table=N
     names = table.podop_names
     pn = (lambda c: names[c]) if names is not None else (lambda c: c)
     return {key: tuple(([(pn(e[0]),) + e[1:] for e in sd[0]],) + sd[1:] for sd in rows[c]) for key, c in zip(ops, codes)}
+
+
+def _per_window(v, n, what):
+    """A bucket origin / width keyword as n Python ints: one value for every window, or one per window."""
+    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+        return [int(v)] * n
+    out = [int(x) for x in v]
+    if len(out) != n:
+        raise ValueError(f"{what} holds {len(out)} values for {n} windows")
+    return out
+
+
+def windows_timeline(ctx, windows, ops, *, buckets=30, what="self", origin=None, width=None):
+    """When inside each window did it happen (mr_windows_timeline, csrc/mr_timeline.hip)?  ``windows`` as
+    rank_windows'; ``ops`` one sequence per window of pod-op codes, -1 standing for the window's own
+    traces.  Returns per window {code or -1: {"start": int64[B], "cnt": int64[B, 2], "sum": int64[B, 2],
+    "max": int64[B, 2], "out": int64[2, 2]}}: the window cut into B = ``buckets`` time buckets by TRACE
+    start, ``start`` each bucket's first ns; per bucket and side (0 normal, 1 abnormal, the window's own
+    detector partition) the op's spans whose trace starts in the bucket, the sum (int64, wrapping) and the
+    largest of their values in raw duration units -- ``what``: "self" (duration minus the children's) or
+    "duration"; for -1 the traces, each once, valued endTime - startTime; ``max`` is 0 where ``cnt`` is 0 --
+    and ``out[side]`` the spans (traces) that start before / after the bucket range.
+    Bucket b covers [origin + b * width, origin + (b + 1) * width): by default origin = the window's t0 and
+    width = (t1 - t0) // B + 1, which puts every start of [t0, t1] into a bucket, so ``out`` is 0; ``origin``
+    / ``width`` (ns; one value, or one per window) choose another grid.  A whole-table window
+    (INT64_MIN, INT64_MAX) needs both.  An empty window (rank_windows' status MR_ERR_VALUE) answers zeros.
+    ValueError for buckets outside 1..512, an unknown what, more than 64 ops in a window, a width <= 0 or
+    len(ops) != len(windows); tables without trace-level times, self time on a trace shard and -1 on a
+    trace shard are not covered (RuntimeError from the library)."""
+    b, wcode = _timeline_args(buckets, what)
+    n = len(windows)
+    if len(ops) != n:
+        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
+    asked = [[int(o) for o in lst] for lst in ops]
+    k = max([len(a) for a in asked] + [1])
+    if k > 64:
+        raise ValueError(f"a window asks {k} ops; at most 64")
+    if n == 0:
+        return []
+    t0 = np.array([int(w[1]) for w in windows], np.int64)
+    t1 = np.array([int(w[2]) for w in windows], np.int64)
+    whole = [int(a) == _lib.INT64_MIN and int(z) == _lib.INT64_MAX for a, z in zip(t0, t1)]
+    if (origin is None or width is None) and any(whole):
+        raise ValueError("a whole-table window has no default buckets: give origin and width")
+    org = _per_window(origin, n, "origin") if origin is not None else [int(a) for a in t0]
+    wid = _per_window(width, n, "width") if width is not None else [(int(z) - int(a)) // b + 1 for a, z in zip(t0, t1)]
+    if any(x <= 0 for x in wid):
+        raise ValueError(f"a bucket width must be positive, not {min(wid)}")
+    b0, bw = np.array(org, np.int64), np.array(wid, np.int64)
+    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
+           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
+    # (windows that share their SLO arrays give the library one pointer: one upload)
+    addr = {}
+    for i, w in enumerate(windows):
+        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
+            addr.setdefault(id(src), a.ctypes.data)
+    spans = (_lib.P * n)(*[w[0].h for w in windows])
+    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
+    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
+    cod = np.zeros((n, k), np.int32)
+    n_ops = np.array([len(a) for a in asked], np.int32)
+    for i, a in enumerate(asked):
+        cod[i, :len(a)] = a
+    cnt, tot, mx = (np.zeros((n, k, b, 2), np.int64) for _ in range(3))
+    out = np.zeros((n, k, 2, 2), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_timeline(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                              ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, wcode, ptr(b0, C.c_int64),
+                                              ptr(bw, C.c_int64), b, ptr(cnt, C.c_int64), ptr(tot, C.c_int64),
+                                              ptr(mx, C.c_int64), ptr(out, C.c_int64), ptr(status, C.c_int32)),
+              "mr_windows_timeline")
+    res = []
+    for i in range(n):
+        start = b0[i] + np.arange(b, dtype=np.int64) * bw[i]   # (int64 that wraps, for grids past the int64 range)
+        res.append({c: {"start": start, "cnt": cnt[i, j].copy(), "sum": tot[i, j].copy(), "max": mx[i, j].copy(),
+                        "out": out[i, j].copy()} for j, c in enumerate(asked[i])})
+    return res
+
+
+def window_timeline(data, start_time, end_time, slo, ops, *, buckets=30, what="self", ctx=None, table=None, dev=None):
+    """windows_timeline for one window by names: {-1: the window's own traces, pod-op: ...} for the pod-ops
+    of ``ops`` (names, or codes), each {"start", "cnt", "sum", "max", "out"} as plain lists of ints over the
+    default buckets (origin = the window's start, width = (end - start) // buckets + 1 ns).  An op that is
+    no pod-op of the table raises ValueError; ops past the call's 64 slots go in further calls."""
+    buckets, _ = _timeline_args(buckets, what)
+    ops = list(ops)
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    codes = _op_codes(table, ops)
+    a3, ok = slo_arrays(table, slo)
+    win = (dev, to_ns(start_time), to_ns(end_time), a3, ok)
+    asked = [-1] + codes
+    rows = {}
+    for b in range(0, len(asked), 64):
+        rows.update(windows_timeline(ctx, [win], [asked[b:b + 64]], buckets=buckets, what=what)[0])
+    return {key: _timeline_lists(rows[c]) for key, c in zip([-1] + ops, asked)}
 
 
 def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):
