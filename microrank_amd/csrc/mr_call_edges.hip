@@ -14,18 +14,12 @@
 //                pair's dense edge id by binary search in ekey.  A window keeps whole traces (trace-level
 //                times) or is the whole table, so the two states alone say that both rows lie in the
 //                window.  Rows of one parent are mostly adjacent and often of one op: runs of equal
-//                (edge id, side) inside a wave are reduced by a segmented scan and the run's last lane
-//                issues three 64-bit atomics -- calls += n, dsum += sum (uint64: int64 sums that wrap,
-//                whatever the order), dmax = max as an unsigned max of the bias-flipped value (v ^ 2^63:
-//                order-preserving, and the zeroed counter is the smallest).  A spanID shared by several
-//                rows: the first parent row goes through the scan, every further one adds its own
-//                pair.  A run's sums do not go to the window's counters at once: a block works through
-//                many tiles of rows and keeps a table of CE_H (edge id, side) slots in LDS (32 KB: key,
-//                calls, dsum, dmax), a slot claimed by the first key whose hash names it; a key that
-//                finds its slot taken adds to the global counters itself, and the block adds its table
-//                to them once, at its end -- a few thousand hot addresses would otherwise take three
-//                global atomics per run of a few rows.  Integer adds and maxima are order-free: the
-//                counters are bitwise reproducible, whatever the cut and whichever path a run took
+//                (edge id, side) inside a wave are reduced (mr_prim.h wave_run_reduce) and the run's
+//                last lane adds calls, dsum and dmax to the block's counter table in LDS (mr_evidence.h
+//                EvTable, hashed), which the block adds to the window's counters once, at its end.  A
+//                spanID shared by several rows: the first parent row goes through the reduction, every
+//                further one adds its own pair.  The counters are bitwise reproducible, whatever the
+//                cut and whichever path a run took
 //   k_ce_select  a block per (window, slice of edge ids), a thread per edge: a live edge (calls > 0 on
 //                either side) whose child is asked is a caller candidate of that slot, whose parent is
 //                asked a callee candidate (the asked codes, distinct, sit in LDS: at most two
@@ -41,19 +35,12 @@
 //   k_ce_merge   a block per (window, slot, direction) merges the blocks' lists (ex_merge_body)
 //   k_ce_finish  the edge id of every answer entry into its peer code and its six counters
 // One row pass per chunk of windows -- never a launch per asked op or per edge -- and one pinned
-// read-back per chunk, which carries the detectors' counts too (an empty window is found there: its
-// states are all 0, so its kernels answered the padding): no host synchronisation per window.  Windows go in chunks whose dense counters (48 bytes per window and edge) stay
-// under CE_SCRATCH_BYTES (MR_CE_CHUNK, read per call, forces the windows per chunk; MR_CE_BLOCKS the
-// blocks per window of the count and of the select pass: tests reach every merge shape at small sizes).
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <tuple>
-#include <vector>
-
+// read-back per chunk, which carries the detectors' counts too: no host synchronisation per window.  The
+// window list's front end is mr_evidence.h's; a chunk's dense counters take 48 bytes per window and edge
+// (MR_CE_CHUNK, read per call, forces the windows per chunk; MR_CE_BLOCKS the blocks per window of the
+// count and of the select pass: tests reach every merge shape at small sizes).
+#include "mr_evidence.h"
 #include "mr_exemplar_dev.h"
-#include "mr_prim.h"
 
 namespace {
 constexpr int CE_U = 4;                       // k_ce_count: rows in flight per lane
@@ -61,11 +48,7 @@ constexpr int CE_TILE = EX_T * CE_U;          // rows of a block's tile
 constexpr int CE_L = EX_MAXOPS * 2;           // lists of a window: (slot, direction)
 constexpr int CE_Q = EX_T * 2;                // most candidates of a select round
 constexpr int CE_W = 6;                       // counter words per edge: [side][calls, dsum, biased dmax]
-constexpr size_t CE_SCRATCH_BYTES = (size_t)64 << 20;   // a chunk's dense counters
-constexpr int CE_MAX_Y = 32768;               // windows per launch (gridDim.y)
 constexpr int CE_MAX_CB = 4096;               // count blocks per window (grid-stride over the tiles)
-constexpr int CE_HB = 10, CE_H = 1 << CE_HB;  // k_ce_count: slots of a block's counter table in LDS
-constexpr unsigned long long CE_BIAS = 1ull << 63;
 
 struct CeWin {
     const int32_t *podop, *trace, *id_rows;
@@ -92,39 +75,14 @@ __device__ __forceinline__ int64_t ce_eid(const uint64_t* __restrict__ ek, int64
     return lo < E && ek[lo] == k ? lo : -1;
 }
 
-__device__ __forceinline__ void ce_add(unsigned long long* cnt, int64_t kd, unsigned long long n, unsigned long long sum,
-                                       unsigned long long mx) {
-    unsigned long long* p = cnt + kd * 3;   // kd = eid * 2 + side
-    atomicAdd(p, n);
-    atomicAdd(p + 1, sum);
-    atomicMax(p + 2, mx);
-}
-
-// a run's sums into the block's table: the slot of kd's hash, claimed by the first key that comes; a key
-// that finds its slot taken by another goes to the global counters itself (integer adds and maxima
-// either way: the same bits)
-__device__ __forceinline__ void ce_add_block(unsigned long long* hk, unsigned long long* hn, unsigned long long* hs,
-                                             unsigned long long* hm, unsigned long long* cnt, int64_t kd,
-                                             unsigned long long n, unsigned long long sum, unsigned long long mx) {
-    const uint32_t h = (uint32_t)(((unsigned long long)kd * 0x9E3779B97F4A7C15ull) >> (64 - CE_HB));
-    const unsigned long long mine = (unsigned long long)kd + 1ull;
-    const unsigned long long prev = atomicCAS(&hk[h], 0ull, mine);
-    if (prev == 0ull || prev == mine) {
-        atomicAdd(&hn[h], n);
-        atomicAdd(&hs[h], sum);
-        atomicMax(&hm[h], mx);
-    } else {
-        ce_add(cnt, kd, n, sum, mx);
-    }
-}
-
+// (a key of the block's table: kd = edge id * 2 + side)
 __global__ void __launch_bounds__(EX_T) k_ce_count(const CeWin* __restrict__ ws) {
-    __shared__ unsigned long long hk[CE_H], hn[CE_H], hs[CE_H], hm[CE_H];   // key + 1 (0: free), calls, dsum, biased dmax
+    __shared__ EvTable tab;   // calls, dsum, biased dmax
     const CeWin& w = ws[blockIdx.y];
     const int64_t S = w.n_ops ? w.S : 0;   // (nothing asked, or an empty window: nothing is read)
     if ((int64_t)blockIdx.x * CE_TILE >= S) return;   // (block-uniform)
     const int lane = threadIdx.x & (WAVE - 1);
-    for (int i = threadIdx.x; i < CE_H; i += EX_T) hk[i] = hn[i] = hs[i] = hm[i] = 0ull;
+    tab.clear(threadIdx.x, EX_T);
     __syncthreads();
     const int64_t n_codes = w.n_codes, E = w.E;
     const uint32_t NT = (uint32_t)w.NT;
@@ -161,34 +119,18 @@ __global__ void __launch_bounds__(EX_T) k_ce_count(const CeWin* __restrict__ ws)
                             }
                             const int64_t q = id * 2 + (st[k] - 1);
                             if (e == a) kd = q;
-                            else ce_add_block(hk, hn, hs, hm, w.cnt, q, 1ull, d, d ^ CE_BIAS);
+                            else tab.add(false, w.cnt, q, ev_run_of(true, d));
                         }
                     }
                 }
             }
-            unsigned long long n = kd >= 0 ? 1ull : 0ull, v = kd >= 0 ? d : 0ull, mx = kd >= 0 ? d ^ CE_BIAS : 0ull;
-            const int64_t pk = __shfl_up(kd, 1, WAVE);
-            const bool head = lane == 0 || pk != kd;
-            const uint64_t heads = __ballot(head);
-            const int seg = __popcll(heads & (~0ull >> (63 - lane)));   // heads at or below this lane
-#pragma unroll
-            for (int off = 1; off < WAVE; off <<= 1) {
-                const unsigned long long no = __shfl_up(n, off, WAVE), vo = __shfl_up(v, off, WAVE),
-                                         mo = __shfl_up(mx, off, WAVE);
-                const int so = __shfl_up(seg, off, WAVE);
-                if (lane >= off && so == seg) {
-                    n += no;
-                    v += vo;
-                    mx = mo > mx ? mo : mx;
-                }
-            }
-            const bool tail = ((heads >> 1) >> lane & 1ull) || lane == WAVE - 1;   // (the next lane heads a run)
-            if (kd >= 0 && tail) ce_add_block(hk, hn, hs, hm, w.cnt, kd, n, v, mx);
+            EvRun run = ev_run_of(kd >= 0, d);
+            const bool tail = wave_run_reduce(lane, kd, run);
+            if (kd >= 0 && tail) tab.add(false, w.cnt, kd, run);
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < CE_H; i += EX_T)
-        if (hk[i]) ce_add(w.cnt, (int64_t)(hk[i] - 1ull), hn[i], hs[i], hm[i]);
+    tab.flush<int64_t>(false, w.cnt, threadIdx.x, EX_T);
 }
 
 // ps / pt: [list block][KL][m]; tot: [window][KL][3] peers, abnormal, normal calls (zeroed by the caller)
@@ -298,27 +240,12 @@ __global__ void __launch_bounds__(EX_T) k_ce_finish(const CeWin* __restrict__ ws
             const unsigned long long calls = c[side * 3];
             v[side] = (long long)calls;
             v[2 + side] = (long long)c[side * 3 + 1];
-            v[4 + side] = calls ? (long long)(c[side * 3 + 2] ^ CE_BIAS) : 0ll;
+            v[4 + side] = calls ? (long long)(c[side * 3 + 2] ^ EV_BIAS) : 0ll;
         }
     }
     peer[e] = pc;
 #pragma unroll
     for (int k = 0; k < 6; ++k) val[e * 6 + k] = v[k];
-}
-
-int ce_num_cus() {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            v = 256;
-        return std::max(v, 1);
-    }();
-    return ncu;
-}
-
-int ce_env(const char* name) {   // (test knobs, read per call; 0: not set)
-    const char* e = getenv(name);
-    return e ? std::max(atoi(e), 0) : 0;
 }
 }  // namespace
 
@@ -328,24 +255,11 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
                                      int64_t* ce_calls, int64_t* ce_dsum, int64_t* ce_dmax, int32_t* ce_n,
                                      int32_t* ce_peers, int64_t* ce_tot, int32_t* status) {
     const char* who = "mr_windows_call_edges";
-    if (!ctx || n_windows < 0 ||
-        (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !podops || !n_ops || !ce_peer || !ce_calls || !ce_dsum ||
-                       !ce_dmax || !ce_n || !ce_peers || !ce_tot || !status)))
-        return mr_fail(ctx, MR_ERR_ARG, "%s: bad arguments", who);
-    if (K < 1 || K > EX_MAXOPS) return mr_fail(ctx, MR_ERR_ARG, "%s: K = %d is not in 1..%d", who, K, EX_MAXOPS);
+    const EvList L{n_windows, spans, t0, t1, a3, a3_valid, podops, n_ops, K};
+    MR_TRY(ev_check_args(ctx, who, L, !n_windows || (ce_peer && ce_calls && ce_dsum && ce_dmax && ce_n && ce_peers && ce_tot && status),
+                         EX_MAXOPS));
     if (m < 1 || m > EX_MAXM) return mr_fail(ctx, MR_ERR_ARG, "%s: m = %d is not in 1..%d", who, m, EX_MAXM);
-    for (int32_t i = 0; i < n_windows; ++i) {
-        const mr_spans* s = spans[i];
-        if (!s || s->ctx != ctx || !a3[i] || !a3_valid[i]) return mr_fail(ctx, MR_ERR_ARG, "%s: bad window %d", who, i);
-        if (n_ops[i] < 0 || n_ops[i] > K)
-            return mr_fail(ctx, MR_ERR_ARG, "%s: n_ops[%d] = %d is not in 0..%d", who, i, n_ops[i], K);
-        for (int32_t j = 0; j < n_ops[i]; ++j) {
-            const int32_t c = podops[(size_t)i * K + j];
-            if (c < 0 || c >= s->n_podops)
-                return mr_fail(ctx, MR_ERR_ARG, "%s: window %d: podops[%d] = %d is no pod-op code of the table (%d)", who, i,
-                               j, c, s->n_podops);
-        }
-    }
+    MR_TRY(ev_check_windows(ctx, who, L, false));
     for (int32_t i = 0; i < n_windows; ++i) {
         const mr_spans* s = spans[i];
         const bool whole = t0[i] == INT64_MIN && t1[i] == INT64_MAX;
@@ -378,24 +292,13 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
     std::fill(ce_tot, ce_tot + R * 2, (int64_t)0);
     std::fill(status, status + n_windows, (int32_t)MR_OK);
     hipStream_t st = ctx->stream;
-    const int forced_chunk = ce_env("MR_CE_CHUNK"), forced_blocks = ce_env("MR_CE_BLOCKS");
+    const int forced_chunk = knob_int("MR_CE_CHUNK"), forced_blocks = knob_int("MR_CE_BLOCKS");
     const int32_t KL = K * 2;
-    // Windows that give the same SLO arrays for the same number of ops share one upload (the call's).
-    struct Slo {
-        DBuf<double> a3;
-        DBuf<uint8_t> ok;
-    };
-    std::map<std::tuple<const double*, const uint8_t*, int32_t>, Slo> slos;
+    const auto cnt_words = [&](int32_t i) { return (size_t)std::max<int64_t>(spans[i]->n_edge_keys, 1) * CE_W; };
+    EvSlos slos;
     for (int32_t c0 = 0; c0 < n_windows;) {
-        // the chunk: consecutive windows while their dense counters fit the scratch (at least one)
-        int32_t c1 = c0;
         size_t words = 0;
-        while (c1 < n_windows && c1 - c0 < CE_MAX_Y) {
-            const size_t wds = (size_t)std::max<int64_t>(spans[c1]->n_edge_keys, 1) * CE_W;
-            if (forced_chunk ? c1 - c0 >= forced_chunk : (c1 > c0 && (words + wds) * 8 > CE_SCRATCH_BYTES)) break;
-            words += wds;
-            ++c1;
-        }
+        const int32_t c1 = ev_chunk_end(c0, n_windows, forced_chunk, 8, cnt_words, &words);
         const int32_t cw = c1 - c0;
         const size_t row = (size_t)KL * m, nm = (size_t)cw * row, CR = (size_t)cw * KL;
         std::vector<DBuf<uint8_t>> dstate((size_t)cw);
@@ -406,40 +309,23 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
         // ob, the chunk's ONE read-back: [cw * DW] the detectors' counter shards (u64), [1] pairs without an edge
         // id, [CR * 3] totals (u64), [nm] merged keys (u64), [nm * 6] values (i64), then as int32 [nm] peers, [nm]
         // merged edge ids, [CR] counts
-        constexpr size_t DW = 3 * MR_DETECT_SHARDS;
+        constexpr size_t DW = EV_DW;
         const size_t ob_words = (size_t)cw * DW + 1 + CR * 3 + nm + nm * 6 + (2 * nm + CR + 1) / 2;
         MR_TRY(ob.zero(ctx, ob_words));
         std::vector<char> det_async((size_t)cw, 0);
         int32_t n_async = 0;
-        const int64_t blocks_cap = std::max<int64_t>(1, 4 * (int64_t)ce_num_cus() / cw);
-        int64_t nblk = 0, maxS = 0, max_nb = 0;
+        EvBlocks blocks{forced_blocks, ev_block_cap(4, cw), EX_MAXB};
+        int64_t maxS = 0;
         size_t cw0 = 0;
         for (int32_t i = 0; i < cw; ++i) {
             const int32_t gi = c0 + i;
             const mr_spans* s = spans[gi];
             const int32_t NT = s->n_traces;
-            Slo& sl = slos[std::make_tuple(a3[gi], a3_valid[gi], s->n_svcops)];
-            if (!sl.a3.p) {
-                MR_TRY(sl.a3.upload(ctx, a3[gi], (size_t)s->n_svcops));
-                MR_TRY(sl.ok.upload(ctx, a3_valid[gi], (size_t)s->n_svcops));
-            }
-            MR_TRY(dstate[(size_t)i].zero(ctx, (size_t)std::max(NT, 1)));
-            bool empty = false;
-            if (s->indexed && s->uniform_times) {
-                // the per-trace detector, launched only: its counts come back with the chunk's read-back (an
-                // empty window's states are all 0, so its answer is the padding whatever is asked)
-                MR_TRY(mr_detect_indexed_launch(ctx, s, t0[gi], t1[gi], sl.a3.p, sl.ok.p, dstate[(size_t)i].p,
-                                                ob.p + (size_t)i * DW));
-                det_async[(size_t)i] = 1;
-                ++n_async;
-            } else {   // (the whole table of per-span window times: the row-level detector, which reads its sizes back)
-                int32_t na = 0, nn = 0;
-                int64_t nin = 0;
-                const int rc = mr_detect_dev(ctx, s, t0[gi], t1[gi], sl.a3.p, sl.ok.p, dstate[(size_t)i].p, &na, &nn, &nin);
-                empty = rc == MR_ERR_VALUE && nin == 0;   // T2: "Current span list is empty"
-                if (rc != MR_OK && !empty) return rc;
-                if (empty) status[gi] = MR_ERR_VALUE;
-            }
+            // (the whole table of per-span window times goes through the row-level detector)
+            bool launched = false, empty = false;
+            MR_TRY(ev_partition(ctx, L, gi, slos, dstate[(size_t)i], ob.p + (size_t)i * DW, &launched, &empty, status));
+            det_async[(size_t)i] = launched;
+            n_async += launched;
             CeWin& w = hw[(size_t)i];
             memset(&w, 0, sizeof w);
             w.podop = s->podop.p;
@@ -452,29 +338,17 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
             w.state = dstate[(size_t)i].p;
             w.cnt = cnt.p + cw0;
             w.miss = ob.p + (size_t)cw * DW;
-            cw0 += (size_t)std::max<int64_t>(s->n_edge_keys, 1) * CE_W;
+            cw0 += cnt_words(gi);
             w.S = s->S;
             w.n_codes = s->n_span_codes;
             w.E = s->n_edge_keys;
             w.NT = NT;
-            for (int32_t j = 0; j < (empty || NT == 0 || s->S == 0 || s->n_edge_keys == 0 ? 0 : n_ops[gi]); ++j) {
-                const int32_t c = podops[(size_t)gi * K + j];
-                int32_t u = 0;
-                while (u < w.n_ops && w.op[u] != c) ++u;
-                if (u == w.n_ops) w.op[w.n_ops++] = c;
-                rep[(size_t)i * K + j] = u;
-            }
-            int64_t nb = forced_blocks ? forced_blocks : std::min<int64_t>(cdiv(std::max<int64_t>(w.E, 1), EX_T), blocks_cap);
-            nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
-            w.nb = (int32_t)nb;
-            w.per = (std::max<int64_t>(w.E, 1) + nb - 1) / nb;
-            w.b0 = (int32_t)nblk;
-            if (w.n_ops) {
-                nblk += nb;
-                maxS = std::max<int64_t>(maxS, s->S);
-                max_nb = std::max(max_nb, nb);
-            }
+            if (!(empty || NT == 0 || s->S == 0 || s->n_edge_keys == 0))
+                ev_slots(podops + (size_t)gi * K, n_ops[gi], w.op, &w.n_ops, nullptr, &rep[(size_t)i * K]);
+            blocks.add(w.E, cdiv(std::max<int64_t>(w.E, 1), EX_T), w.n_ops != 0, &w.nb, &w.per, &w.b0);
+            if (w.n_ops) maxS = std::max<int64_t>(maxS, s->S);
         }
+        const int64_t nblk = blocks.nblk;
         DBuf<CeWin> dw;
         DBuf<unsigned long long> ps;
         DBuf<int32_t> pt;
@@ -492,11 +366,11 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
             // a block keeps its counters in LDS over all its tiles and adds them to the window's once: few
             // blocks per window where the chunk's windows fill the device anyway
             const int64_t cb = forced_blocks ? std::min<int64_t>(forced_blocks, tiles)
-                                             : std::min<int64_t>(tiles, std::min<int64_t>(CE_MAX_CB, std::max<int64_t>(1, 8 * (int64_t)ce_num_cus() / cw)));
+                                             : std::min<int64_t>(tiles, std::min<int64_t>(CE_MAX_CB, ev_block_cap(8, cw)));
             hipLaunchKernelGGL(k_ce_count, dim3((unsigned)std::max<int64_t>(cb, 1), (unsigned)cw), dim3(EX_T), 0, st,
                                (const CeWin*)dw.p);
-            hipLaunchKernelGGL(k_ce_select, dim3((unsigned)max_nb, (unsigned)cw), dim3(EX_T), 0, st, (const CeWin*)dw.p, KL, m,
-                               ps.p, pt.p, tot);
+            hipLaunchKernelGGL(k_ce_select, dim3((unsigned)blocks.widest, (unsigned)cw), dim3(EX_T), 0, st, (const CeWin*)dw.p,
+                               KL, m, ps.p, pt.p, tot);
             hipLaunchKernelGGL(k_ce_merge, dim3((unsigned)CR), dim3(EX_T), 0, st, (const CeWin*)dw.p, KL, m,
                                (const unsigned long long*)ps.p, (const int32_t*)pt.p, os, ot, on);
             hipLaunchKernelGGL(k_ce_finish, dim3((unsigned)cdiv((int64_t)nm, EX_T)), dim3(EX_T), 0, st, (const CeWin*)dw.p, KL,
@@ -504,23 +378,8 @@ extern "C" int mr_windows_call_edges(mr_ctx* ctx, int32_t n_windows, const mr_sp
             MR_TRY_HIP(ctx, hipGetLastError());
         }
         if (nblk > 0 || n_async > 0) {
-            if (ctx->pin_ex_n < ob_words) {
-                if (ctx->pin_ex) (void)hipHostFree(ctx->pin_ex);
-                ctx->pin_ex = nullptr;
-                ctx->pin_ex_n = 0;
-                if (hipHostMalloc((void**)&ctx->pin_ex, ob_words * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-                    return mr_fail(ctx, MR_ERR_OOM, "%s: pinned read-back words", who);
-                ctx->pin_ex_n = ob_words;
-            }
-            MR_TRY_HIP(ctx, hipMemcpyAsync(ctx->pin_ex, ob.p, ob_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            MR_TRY_HIP(ctx, hipStreamSynchronize(st));
-            for (int32_t i = 0; i < cw; ++i) {
-                if (!det_async[(size_t)i]) continue;
-                int32_t na = 0, nn = 0;
-                int64_t nin = 0;
-                mr_detect_sum(ctx->pin_ex + (size_t)i * DW, &na, &nn, &nin);
-                if (nin == 0) status[c0 + i] = MR_ERR_VALUE;   // T2: "Current span list is empty"
-            }
+            MR_TRY(mr_pin_ex(ctx, ob.p, ob_words, who));
+            ev_launched_status(ctx->pin_ex, det_async, c0, status);
             if (ctx->pin_ex[(size_t)cw * DW])
                 return mr_fail(ctx, MR_ERR_STATE, "%s: %llu call pairs have no id in their table's edge dictionary (the index "
                                "and the join disagree)", who, ctx->pin_ex[(size_t)cw * DW]);

@@ -30,13 +30,9 @@
 // Order: score descending, trace index ascending on equal fp64 values.  Scores are non-negative, so
 // (score bits, trace index) is a total order and the answer does not depend on how the traces are cut
 // into blocks (MR_EX_BLOCKS, read per call, forces the block count: tests reach the merge at tiny sizes).
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-
+#include "mr_evidence.h"       // the asked ops' slots, the list-block plan, the pinned read-back
 #include "mr_exemplar_dev.h"   // the lists: order, insert, drain, merge (shared with mr_kind_breakdown.hip)
 #include "mr_iter_dev.h"
-#include "mr_prim.h"
 
 constexpr int EX_HT = 256;         // slots of the asked ops' hash table (load <= 1/4)
 constexpr int EX_U = 4;            // ids per thread and round of k_ex_select
@@ -380,16 +376,6 @@ __global__ void __launch_bounds__(EX_T) k_win_ex_merge(const WXDev* __restrict__
                       DK ? pm + pb : nullptr, DK ? om + ob : nullptr);
 }
 
-static int ex_num_cus() {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            v = 256;
-        return std::max(v, 1);
-    }();
-    return ncu;
-}
-
 // shard: the sharded entries' form -- this rank's traces of a graph whose last ranking was
 // mr_pagerank_sharded(_converge): q holds them, the ring's r half the WHOLE graph's M_r(K)
 // (rmax_take_*), sub[(K-1) & 1] and the s half are replicated, v0 counts every rank's traces
@@ -440,12 +426,7 @@ extern "C" int mr_graph_trace_rank(mr_graph* g, double* r) {
 // distinct ops for the kernels; request i is answered from slot[i]
 static void ex_request(const int32_t* ops, int32_t n_ops, ExReq& rq, int32_t* slot) {
     memset(&rq, 0, sizeof rq);
-    for (int32_t i = 0; i < n_ops; ++i) {
-        int32_t u = 0;
-        while (u < rq.n && rq.op[u] != ops[i]) ++u;
-        if (u == rq.n) rq.op[rq.n++] = ops[i];
-        slot[i] = u;
-    }
+    ev_slots(ops, n_ops, rq.op, &rq.n, nullptr, slot);
 }
 // A graph's own lists for a request: k_ex_select over its traces, k_ex_merge over the blocks, into ob --
 // [nu * m] score bits, then as int32 [nu * m] traces, [nu] counts and (dk) [nu * m] class sizes.  The
@@ -464,11 +445,9 @@ static int ex_local_lists(mr_ctx* ctx, mr_graph* g, const ExReq& rq, int32_t m, 
     // (T == 0, an empty shard: one block that reads nothing and writes empty lists)
     const int64_t* off = g->rs_is_sr ? g->rs_off.p : g->srt_off.p;
     if (!off && T > 0) return mr_fail(ctx, MR_ERR_STATE, "mr_graph_exemplars: the graph has no trace-major incidence");
-    int64_t nb = std::min<int64_t>(cdiv(std::max(T, 1), EX_T), 2 * (int64_t)ex_num_cus());
-    if (const char* e = getenv("MR_EX_BLOCKS"))   // (test knob, read per call)
-        if (atoi(e) > 0) nb = atoi(e);
-    nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
-    const int32_t per = cdiv(std::max(T, 1), nb);
+    EvBlocks blocks{knob_int("MR_EX_BLOCKS"), ev_block_cap(2, 1), EX_MAXB};
+    int32_t nb = 0, per = 0, b0 = 0;
+    blocks.add(T, cdiv(std::max(T, 1), EX_T), true, &nb, &per, &b0);
     MR_TRY(L.ps.alloc(ctx, (size_t)nb * nm));
     MR_TRY(L.pt.alloc(ctx, (size_t)nb * nm));
     if (dk) {
@@ -770,13 +749,9 @@ int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m, uint32_t 
     }
     if (!lo.empty()) {
         const int nw = (int)lo.size();
-        int forced = 0;
-        if (const char* e = getenv("MR_EX_BLOCKS"))   // (test knob, read per call)
-            forced = std::max(atoi(e), 0);
-        const int64_t cap = std::max<int64_t>(1, 4 * (int64_t)ex_num_cus() / nw);
+        EvBlocks blocks{knob_int("MR_EX_BLOCKS"), ev_block_cap(4, nw), EX_MAXB};
         std::vector<WXDev> hd((size_t)nw);
         int32_t KO = 1, maxN = 0;
-        int64_t nblk = 0;
         for (int i = 0; i < nw; ++i) {
             const MrWinEx& w = ws[lo[(size_t)i]];
             const mr_graph* g = w.g;
@@ -804,16 +779,12 @@ int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m, uint32_t 
             v.n_wt = g->n_wt;
             v.K = w.K;
             v.n_ops = w.n_ops;
-            int64_t nb = forced ? forced : std::min<int64_t>(cdiv(g->n_wt, 16), cap);
-            nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
-            v.nb = (int32_t)nb;
-            v.per = cdiv(std::max(g->n_wt, 1), nb);
-            v.b0 = (int32_t)nblk;
-            nblk += nb;
+            blocks.add(g->n_wt, cdiv(g->n_wt, 16), true, &v.nb, &v.per, &v.b0);
             memcpy(v.op, w.ops, (size_t)w.n_ops * sizeof(int32_t));
             KO = std::max(KO, w.n_ops);
             maxN = std::max(maxN, g->N);
         }
+        const int64_t nblk = blocks.nblk;
         if (nblk >= (1ll << 31)) return mr_fail(ctx, MR_ERR_ARG, "mr_win_exemplars: too many blocks");
         DBuf<WXDev> dd;
         // ob: [nw * KO * m] score bits, then as int32 [nw * KO * m] traces, [nw * KO] counts, (dk) [nw * KO * m] class sizes
@@ -837,16 +808,7 @@ int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m, uint32_t 
                            (const WXDev*)dd.p, KO, m, (const unsigned long long*)ps.p, (const int32_t*)pt.p, ob.p, ot,
                            ot + nm, (const int32_t*)pk.p, (const int32_t*)pm.p, ot + nm + (size_t)nw * KO);
         MR_TRY_HIP(ctx, hipGetLastError());
-        if (ctx->pin_ex_n < ob_words) {
-            if (ctx->pin_ex) (void)hipHostFree(ctx->pin_ex);
-            ctx->pin_ex = nullptr;
-            ctx->pin_ex_n = 0;
-            if (hipHostMalloc((void**)&ctx->pin_ex, ob_words * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-                return mr_fail(ctx, MR_ERR_OOM, "mr_win_exemplars: pinned read-back words");
-            ctx->pin_ex_n = ob_words;
-        }
-        MR_TRY_HIP(ctx, hipMemcpyAsync(ctx->pin_ex, ob.p, ob_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        MR_TRY_HIP(ctx, hipStreamSynchronize(st));
+        MR_TRY(mr_pin_ex(ctx, ob.p, ob_words, "mr_win_exemplars"));
         const double* hs = (const double*)ctx->pin_ex;
         const int32_t* hts = (const int32_t*)(ctx->pin_ex + nm);
         const int32_t* hn = hts + nm;

@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -61,9 +63,8 @@ struct mr_ctx {
     // pinned error words of the PageRank groups a window batch has in flight (grown per call)
     int32_t* pin_flags = nullptr;
     size_t pin_flags_n = 0;
-    // pinned words of a window batch's exemplar read-back (mr_windows_batch_exemplars), of a kind
-    // breakdown chunk's (mr_windows_kind_breakdown) and of a call-evidence chunk's (mr_windows_call_edges);
-    // grown per call
+    // pinned words of the one large read-back that ends a launch sequence (mr_evidence.h mr_pin_ex: a
+    // window batch's exemplar rows, an evidence chunk's answers); grown per call, never shrunk
     unsigned long long* pin_ex = nullptr;
     size_t pin_ex_n = 0;
     // one-shot peer all-reduce (mr_comm_peer_enable; mr_comm.hip): a receive region in uncached
@@ -490,6 +491,20 @@ struct PhaseTimer {
 
 // Launch helpers
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+inline int num_cus() {
+    static const int ncu = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            v = 256;
+        return std::max(v, 1);
+    }();
+    return ncu;
+}
+// a test knob as a non-negative int (read per call: tests set them; 0: not set)
+inline int knob_int(const char* name) {
+    const char* e = getenv(name);
+    return e ? std::max(atoi(e), 0) : 0;
+}
 
 int mr_graph_prepare(mr_ctx* ctx, mr_graph* g);   // derived arrays + segments after structure upload
 // several graphs' prepare in one launch per step when they allow it (keep: host descriptors)

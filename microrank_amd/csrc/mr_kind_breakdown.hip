@@ -25,25 +25,17 @@
 //   k_kb_merge   a block per (window, slot) merges the blocks' lists (ex_merge_body)
 //   k_kb_finish  key and rep of every answer entry into the five output columns; spans and ops of
 //                a kind are its rep's tlen and po_off difference (every member has the same)
-// One pinned read-back per chunk.  Windows go in chunks whose dense counters stay under
-// KB_SCRATCH_BYTES (MR_KB_CHUNK, read per call, forces the windows per chunk; MR_KB_BLOCKS the select
-// blocks per window: tests reach every merge shape at small sizes).
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <tuple>
-#include <vector>
-
+// One pinned read-back per chunk.  The window list's front end is mr_evidence.h's (each window's detector
+// synchronises); a chunk's dense counters take 16 bytes per window and kind (MR_KB_CHUNK, read per call,
+// forces the windows per chunk; MR_KB_BLOCKS the select blocks per window: tests reach every merge shape
+// at small sizes).
+#include "mr_evidence.h"
 #include "mr_exemplar_dev.h"
-#include "mr_prim.h"
 
 namespace {
 constexpr int KB_U = 4;                       // k_kb_count: layout indices per lane; k_kb_select: codes per kind and round
 constexpr int KB_PMAX = 4096;                 // pod-op codes of a table with a layout order (mr_lo_fits)
 constexpr int KB_Q = EX_T * KB_U;             // most candidates of a round
-constexpr size_t KB_SCRATCH_BYTES = (size_t)64 << 20;   // a chunk's dense counters (16 B per window and kind)
-constexpr int KB_MAX_Y = 32768;               // windows per launch (gridDim.y)
 
 struct KbWin {
     const int32_t *lo_tr, *lo_kid, *tlen;
@@ -55,6 +47,20 @@ struct KbWin {
     int32_t b0, nb, per;          // first list block, select blocks, kinds per block
     int32_t n_ops, all_slot;      // distinct asked slots; the slot of -1 (or -1: not asked)
     int32_t op[EX_MAXOPS];        // asked codes by slot (-1 at all_slot)
+};
+
+// wave_run_reduce's payload: the abnormal | normal << 16 counts of a run (<= 64 each) and the maxima of ~layout
+// index over its abnormal and over its normal members
+struct KbRun {
+    uint32_t c, ma, mn;
+    __device__ __forceinline__ KbRun up(int off) const {
+        return KbRun{__shfl_up(c, off, WAVE), __shfl_up(ma, off, WAVE), __shfl_up(mn, off, WAVE)};
+    }
+    __device__ __forceinline__ void merge(const KbRun& lower) {
+        c += lower.c;
+        ma = max(ma, lower.ma);
+        mn = max(mn, lower.mn);
+    }
 };
 
 __global__ void __launch_bounds__(EX_T) k_kb_count(const KbWin* __restrict__ ws) {
@@ -77,32 +83,17 @@ __global__ void __launch_bounds__(EX_T) k_kb_count(const KbWin* __restrict__ ws)
     for (int k = 0; k < KB_U; ++k) {
         const uint32_t l = (uint32_t)(base + k * EX_T + threadIdx.x);
         const int32_t kd = (uint32_t)kid[k] < (uint32_t)w.nk ? kid[k] : -1;
-        uint32_t c = st[k] == 2 ? 1u : st[k] == 1 ? 0x10000u : 0u;   // abnormal | normal << 16 (<= 64 each)
-        uint32_t ma = st[k] == 2 ? ~l : 0u, mn = st[k] == 1 ? ~l : 0u;   // (l < 2^31: ~l > 0)
-        const int32_t pk = __shfl_up(kd, 1, WAVE);
-        const bool head = lane == 0 || pk != kd;
-        const uint64_t heads = __ballot(head);
-        const int seg = __popcll(heads & (~0ull >> (63 - lane)));   // heads at or below this lane
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            const uint32_t co = __shfl_up(c, off, WAVE), ao = __shfl_up(ma, off, WAVE), no = __shfl_up(mn, off, WAVE);
-            const int so = __shfl_up(seg, off, WAVE);
-            if (lane >= off && so == seg) {
-                c += co;
-                ma = max(ma, ao);
-                mn = max(mn, no);
-            }
-        }
-        const bool tail = ((heads >> 1) >> lane & 1ull) || lane == WAVE - 1;   // (the next lane heads a run)
-        if (kd >= 0 && tail && c) {
+        KbRun r{st[k] == 2 ? 1u : st[k] == 1 ? 0x10000u : 0u, st[k] == 2 ? ~l : 0u, st[k] == 1 ? ~l : 0u};   // (l < 2^31: ~l > 0)
+        const bool tail = wave_run_reduce(lane, kd, r);
+        if (kd >= 0 && tail && r.c) {
             uint32_t* p = w.cnt + (size_t)kd * 4;
-            if (c & 0xFFFFu) {
-                atomicAdd(p, c & 0xFFFFu);
-                atomicMax(p + 2, ma);
+            if (r.c & 0xFFFFu) {
+                atomicAdd(p, r.c & 0xFFFFu);
+                atomicMax(p + 2, r.ma);
             }
-            if (c >> 16) {
-                atomicAdd(p + 1, c >> 16);
-                atomicMax(p + 3, mn);
+            if (r.c >> 16) {
+                atomicAdd(p + 1, r.c >> 16);
+                atomicMax(p + 3, r.mn);
             }
         }
     }
@@ -255,21 +246,6 @@ __global__ void __launch_bounds__(EX_T) k_kb_finish(const KbWin* __restrict__ ws
     col[3 * n + e] = in ? G.tlen[t] : 0;
     col[4 * n + e] = in ? (int32_t)(G.po_off[t + 1] - G.po_off[t]) : 0;
 }
-
-int kb_num_cus() {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            v = 256;
-        return std::max(v, 1);
-    }();
-    return ncu;
-}
-
-int kb_env(const char* name) {   // (test knobs, read per call; 0: not set)
-    const char* e = getenv(name);
-    return e ? std::max(atoi(e), 0) : 0;
-}
 }  // namespace
 
 extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
@@ -279,24 +255,11 @@ extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const m
                                          int32_t* kb_ops, int32_t* kb_n, int32_t* kb_kinds, int64_t* kb_tot,
                                          int32_t* status) {
     const char* who = "mr_windows_kind_breakdown";
-    if (!ctx || n_windows < 0 ||
-        (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !podops || !n_ops || !kb_trace || !kb_abn || !kb_nor ||
-                       !kb_spans || !kb_ops || !kb_n || !kb_kinds || !kb_tot || !status)))
-        return mr_fail(ctx, MR_ERR_ARG, "%s: bad arguments", who);
-    if (K < 1 || K > EX_MAXOPS) return mr_fail(ctx, MR_ERR_ARG, "%s: K = %d is not in 1..%d", who, K, EX_MAXOPS);
+    const EvList L{n_windows, spans, t0, t1, a3, a3_valid, podops, n_ops, K};
+    MR_TRY(ev_check_args(ctx, who, L, !n_windows || (kb_trace && kb_abn && kb_nor && kb_spans && kb_ops && kb_n && kb_kinds && kb_tot && status),
+                         EX_MAXOPS));
     if (m < 1 || m > EX_MAXM) return mr_fail(ctx, MR_ERR_ARG, "%s: m = %d is not in 1..%d", who, m, EX_MAXM);
-    for (int32_t i = 0; i < n_windows; ++i) {
-        const mr_spans* s = spans[i];
-        if (!s || s->ctx != ctx || !a3[i] || !a3_valid[i]) return mr_fail(ctx, MR_ERR_ARG, "%s: bad window %d", who, i);
-        if (n_ops[i] < 0 || n_ops[i] > K)
-            return mr_fail(ctx, MR_ERR_ARG, "%s: n_ops[%d] = %d is not in 0..%d", who, i, n_ops[i], K);
-        for (int32_t j = 0; j < n_ops[i]; ++j) {
-            const int32_t c = podops[(size_t)i * K + j];
-            if (c < -1 || c >= s->n_podops)
-                return mr_fail(ctx, MR_ERR_ARG, "%s: window %d: podops[%d] = %d is neither -1 nor a pod-op code of the table (%d)",
-                               who, i, j, c, s->n_podops);
-        }
-    }
+    MR_TRY(ev_check_windows(ctx, who, L, true));
     for (int32_t i = 0; i < n_windows; ++i) {
         const mr_spans* s = spans[i];
         if (s->grow.p)
@@ -322,23 +285,12 @@ extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const m
     std::fill(kb_tot, kb_tot + R * 2, (int64_t)0);
     std::fill(status, status + n_windows, (int32_t)MR_OK);
     hipStream_t st = ctx->stream;
-    const int forced_chunk = kb_env("MR_KB_CHUNK"), forced_blocks = kb_env("MR_KB_BLOCKS");
-    // Windows that give the same SLO arrays for the same number of ops share one upload (the call's).
-    struct Slo {
-        DBuf<double> a3;
-        DBuf<uint8_t> ok;
-    };
-    std::map<std::tuple<const double*, const uint8_t*, int32_t>, Slo> slos;
+    const int forced_chunk = knob_int("MR_KB_CHUNK"), forced_blocks = knob_int("MR_KB_BLOCKS");
+    const auto cnt_words = [&](int32_t i) { return (size_t)std::max(spans[i]->lo_nk, 1) * 4; };   // (32-bit words)
+    EvSlos slos;
     for (int32_t c0 = 0; c0 < n_windows;) {
-        // the chunk: consecutive windows while their dense counters fit the scratch (at least one)
-        int32_t c1 = c0;
         size_t words = 0;
-        while (c1 < n_windows && c1 - c0 < KB_MAX_Y) {
-            const size_t wds = (size_t)std::max(spans[c1]->lo_nk, 1) * 4;
-            if (forced_chunk ? c1 - c0 >= forced_chunk : (c1 > c0 && (words + wds) * 4 > KB_SCRATCH_BYTES)) break;
-            words += wds;
-            ++c1;
-        }
+        const int32_t c1 = ev_chunk_end(c0, n_windows, forced_chunk, 4, cnt_words, &words);
         const int32_t cw = c1 - c0;
         const size_t row = (size_t)K * m, nm = (size_t)cw * row, CR = (size_t)cw * K;
         std::vector<DBuf<uint8_t>> dstate((size_t)cw);
@@ -346,25 +298,15 @@ extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const m
         std::vector<int32_t> rep(CR, -1);   // the slot that answers asked entry j (a duplicate: its first appearance's)
         DBuf<uint32_t> cnt;
         MR_TRY(cnt.zero(ctx, words));
-        const int64_t blocks_cap = std::max<int64_t>(1, 4 * (int64_t)kb_num_cus() / cw);
-        int64_t nblk = 0, maxNT = 0, max_nb = 0;
+        EvBlocks blocks{forced_blocks, ev_block_cap(4, cw), EX_MAXB};
+        int64_t maxNT = 0;
         size_t cw0 = 0;
         for (int32_t i = 0; i < cw; ++i) {
             const int32_t gi = c0 + i;
             const mr_spans* s = spans[gi];
             const int32_t NT = s->n_traces;
-            Slo& sl = slos[std::make_tuple(a3[gi], a3_valid[gi], s->n_svcops)];
-            if (!sl.a3.p) {
-                MR_TRY(sl.a3.upload(ctx, a3[gi], (size_t)s->n_svcops));
-                MR_TRY(sl.ok.upload(ctx, a3_valid[gi], (size_t)s->n_svcops));
-            }
-            MR_TRY(dstate[(size_t)i].zero(ctx, (size_t)std::max(NT, 1)));
-            int32_t na = 0, nn = 0;
-            int64_t nin = 0;
-            const int rc = mr_detect_dev(ctx, s, t0[gi], t1[gi], sl.a3.p, sl.ok.p, dstate[(size_t)i].p, &na, &nn, &nin);
-            const bool empty = rc == MR_ERR_VALUE && nin == 0;   // T2: "Current span list is empty"
-            if (rc != MR_OK && !empty) return rc;
-            if (empty) status[gi] = MR_ERR_VALUE;
+            bool launched = false, empty = false;
+            MR_TRY(ev_partition(ctx, L, gi, slos, dstate[(size_t)i], nullptr, &launched, &empty, status));
             KbWin& w = hw[(size_t)i];
             memset(&w, 0, sizeof w);
             w.lo_tr = s->lo_tr.p;
@@ -375,31 +317,16 @@ extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const m
             w.lo16 = s->lo16.p;
             w.state = dstate[(size_t)i].p;
             w.cnt = cnt.p + cw0;
-            cw0 += (size_t)std::max(s->lo_nk, 1) * 4;
+            cw0 += cnt_words(gi);
             w.NT = NT;
             w.nk = s->lo_nk;
             w.all_slot = -1;
-            for (int32_t j = 0; j < (empty || NT == 0 || s->lo_nk == 0 ? 0 : n_ops[gi]); ++j) {
-                const int32_t c = podops[(size_t)gi * K + j];
-                int32_t u = 0;
-                while (u < w.n_ops && w.op[u] != c) ++u;
-                if (u == w.n_ops) {
-                    w.op[w.n_ops++] = c;
-                    if (c < 0) w.all_slot = u;
-                }
-                rep[(size_t)i * K + j] = u;
-            }
-            int64_t nb = forced_blocks ? forced_blocks : std::min<int64_t>(cdiv(std::max(w.nk, 1), EX_T), blocks_cap);
-            nb = std::max<int64_t>(1, std::min<int64_t>(nb, EX_MAXB));
-            w.nb = (int32_t)nb;
-            w.per = cdiv(std::max(w.nk, 1), nb);
-            w.b0 = (int32_t)nblk;
-            if (w.n_ops) {
-                nblk += nb;
-                maxNT = std::max<int64_t>(maxNT, NT);
-                max_nb = std::max(max_nb, nb);
-            }
+            if (!(empty || NT == 0 || s->lo_nk == 0))
+                ev_slots(podops + (size_t)gi * K, n_ops[gi], w.op, &w.n_ops, &w.all_slot, &rep[(size_t)i * K]);
+            blocks.add(w.nk, cdiv(std::max(w.nk, 1), EX_T), w.n_ops != 0, &w.nb, &w.per, &w.b0);
+            if (w.n_ops) maxNT = std::max<int64_t>(maxNT, NT);
         }
+        const int64_t nblk = blocks.nblk;
         if (nblk > 0) {
             // ob: [CR * 3] totals (u64), [nm] merged keys (u64), then as int32 [5][nm] columns, [nm] merged reps, [CR] counts
             DBuf<KbWin> dw;
@@ -417,23 +344,14 @@ extern "C" int mr_windows_kind_breakdown(mr_ctx* ctx, int32_t n_windows, const m
             int32_t* on = ot + nm;
             hipLaunchKernelGGL(k_kb_count, dim3((unsigned)cdiv(maxNT, EX_T * KB_U), (unsigned)cw), dim3(EX_T), 0, st,
                                (const KbWin*)dw.p);
-            hipLaunchKernelGGL(k_kb_select, dim3((unsigned)max_nb, (unsigned)cw), dim3(EX_T), 0, st, (const KbWin*)dw.p, K, m,
-                               ps.p, pt.p, tot);
+            hipLaunchKernelGGL(k_kb_select, dim3((unsigned)blocks.widest, (unsigned)cw), dim3(EX_T), 0, st, (const KbWin*)dw.p,
+                               K, m, ps.p, pt.p, tot);
             hipLaunchKernelGGL(k_kb_merge, dim3((unsigned)CR), dim3(EX_T), 0, st, (const KbWin*)dw.p, K, m,
                                (const unsigned long long*)ps.p, (const int32_t*)pt.p, os, ot, on);
             hipLaunchKernelGGL(k_kb_finish, dim3((unsigned)cdiv((int64_t)nm, EX_T)), dim3(EX_T), 0, st, (const KbWin*)dw.p, K,
                                m, (int64_t)nm, (const unsigned long long*)os, (const int32_t*)ot, (const int32_t*)on, col);
             MR_TRY_HIP(ctx, hipGetLastError());
-            if (ctx->pin_ex_n < ob_words) {
-                if (ctx->pin_ex) (void)hipHostFree(ctx->pin_ex);
-                ctx->pin_ex = nullptr;
-                ctx->pin_ex_n = 0;
-                if (hipHostMalloc((void**)&ctx->pin_ex, ob_words * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-                    return mr_fail(ctx, MR_ERR_OOM, "%s: pinned read-back words", who);
-                ctx->pin_ex_n = ob_words;
-            }
-            MR_TRY_HIP(ctx, hipMemcpyAsync(ctx->pin_ex, ob.p, ob_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            MR_TRY_HIP(ctx, hipStreamSynchronize(st));
+            MR_TRY(mr_pin_ex(ctx, ob.p, ob_words, who));
             const unsigned long long* htot = ctx->pin_ex;
             const int32_t* hcol = (const int32_t*)(ctx->pin_ex + CR * 3 + nm);
             const int32_t* hn = hcol + 6 * nm;

@@ -14,15 +14,11 @@
 //                 class = (window * K + slot) * 2 + side; the asked codes of a window sit in LDS
 //   mr_radix_sort, k_lat_bounds, k_lat_pick: ONE sort, one bounds pass and one pick launch for the
 //                 whole call; the order-statistic arithmetic is mr_quantile_dev.h's
-// DB = bits of (vmax - vmin); bits(n_windows * K * 2) + DB > 64 is MR_ERR_ARG.
-#include <algorithm>
+// DB = bits of (vmax - vmin); bits(n_windows * K * 2) + DB > 64 is MR_ERR_ARG.  mr_windows_latency's
+// window list goes through mr_evidence.h's front end (each window's detector synchronises).
 #include <climits>
-#include <map>
-#include <tuple>
-#include <utility>
-#include <vector>
 
-#include "mr_prim.h"
+#include "mr_evidence.h"
 #include "mr_quantile_dev.h"
 #include "mr_sort.h"
 
@@ -45,27 +41,22 @@ struct LatWin {
 
 // csum[parent[i]] += duration[i].  A span's children are mostly adjacent rows, so a per-row atomic
 // would serialise lanes on one address: each run of equal parents among consecutive lanes is summed
-// by a segmented scan (run ids from the head flags, so only contiguous lanes combine) and its last
-// lane alone issues the atomic.  uint64 adds: int64 sums that wrap, whatever the arrival order.
+// (wave_run_reduce) and its last lane alone issues the atomic.  uint64 adds: int64 sums that wrap,
+// whatever the arrival order.
+struct LatSum {
+    unsigned long long v;
+    __device__ __forceinline__ LatSum up(int off) const { return LatSum{__shfl_up(v, off, WAVE)}; }
+    __device__ __forceinline__ void merge(const LatSum& lower) { v += lower.v; }
+};
 __global__ void __launch_bounds__(LT) k_lat_csum(const int64_t* parent, const int64_t* dur, int64_t S, int64_t n_codes,
                                                  unsigned long long* csum) {
     const int64_t i = (int64_t)blockIdx.x * LT + threadIdx.x;
     const int lane = threadIdx.x & (WAVE - 1);
     int64_t p = i < S ? parent[i] : -1;
     if (p < 0 || p >= n_codes) p = -1;   // no parent / an orphan's code: contributes nothing
-    unsigned long long v = p >= 0 ? (unsigned long long)dur[i] : 0ull;
-    const int64_t pp = __shfl_up(p, 1, WAVE);
-    const bool head = lane == 0 || pp != p;
-    const uint64_t heads = __ballot(head);
-    const int seg = __popcll(heads & (~0ull >> (63 - lane)));   // heads at or below this lane
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const unsigned long long vo = __shfl_up(v, off, WAVE);
-        const int so = __shfl_up(seg, off, WAVE);
-        if (lane >= off && so == seg) v += vo;
-    }
-    const bool tail = ((heads >> 1) >> lane & 1ull) || lane == WAVE - 1;   // (the next lane heads a run)
-    if (p >= 0 && tail) atomicAdd(&csum[p], v);
+    LatSum sum{p >= 0 ? (unsigned long long)dur[i] : 0ull};
+    const bool tail = wave_run_reduce(lane, p, sum);
+    if (p >= 0 && tail) atomicAdd(&csum[p], sum.v);
 }
 
 // words: [0] selected rows (COUNT) / append cursor (WRITE), [1] min, [2] max of the selected values
@@ -240,9 +231,7 @@ int lat_args(mr_ctx* ctx, const char* who, int what, const double* q, int32_t n_
 int lat_run(mr_ctx* ctx, const char* who, int64_t nw, const LatReq* rq, int32_t K, int what, const double* q, int32_t n_q,
             int method, double* out, int64_t* count) {
     hipStream_t st = ctx->stream;
-    // a window's distinct asked codes take the slots of their first appearance; a duplicate is
-    // answered from its first appearance's classes (rep)
-    std::vector<LatWin> hw((size_t)nw);
+    std::vector<LatWin> hw((size_t)nw);   // (rep: the slot whose classes answer an asked entry)
     std::vector<int32_t> rep((size_t)nw * K, -1);
     int64_t maxS = 0;
     for (int64_t i = 0; i < nw; ++i) {
@@ -254,12 +243,7 @@ int lat_run(mr_ctx* ctx, const char* who, int64_t nw, const LatReq* rq, int32_t 
         w = LatWin{s->podop.p, s->trace.p, s->duration.p, s->span.p, (whole || r.by_state) ? nullptr : s->tstart.p,
                    (whole || r.by_state) ? nullptr : s->tend.p, what == MR_LAT_SELF ? s->csum.p : nullptr, r.d_state, s->S,
                    r.t0, r.t1, s->n_span_codes, i * K * 2, s->n_traces, 0, {}};
-        for (int32_t j = 0; j < r.n_ops; ++j) {
-            int32_t u = 0;
-            while (u < w.n_ops && w.ops[u] != r.ops[j]) ++u;
-            if (u == w.n_ops) w.ops[w.n_ops++] = r.ops[j];
-            rep[(size_t)(i * K + j)] = u;
-        }
+        ev_slots(r.ops, r.n_ops, w.ops, &w.n_ops, nullptr, &rep[(size_t)(i * K)]);
         if (s->S == 0) w.n_ops = 0;
         if (w.n_ops) maxS = std::max(maxS, s->S);
     }
@@ -358,23 +342,10 @@ extern "C" int mr_windows_latency(mr_ctx* ctx, int32_t n_windows, const mr_spans
                                   const int32_t* podops, const int32_t* n_ops, int32_t K, int what, const double* q,
                                   int32_t n_q, int method, double* out, int64_t* count, int32_t* status) {
     const char* who = "mr_windows_latency";
-    if (!ctx || n_windows < 0 || !q ||
-        (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !podops || !n_ops || !out || !count || !status)))
-        return mr_fail(ctx, MR_ERR_ARG, "%s: bad arguments", who);
-    if (K < 1 || K > LAT_MAX_OPS) return mr_fail(ctx, MR_ERR_ARG, "%s: K = %d is not in 1..%d", who, K, LAT_MAX_OPS);
+    const EvList L{n_windows, spans, t0, t1, a3, a3_valid, podops, n_ops, K};
+    MR_TRY(ev_check_args(ctx, who, L, q && (!n_windows || (out && count && status)), LAT_MAX_OPS));
     MR_TRY(lat_args(ctx, who, what, q, n_q, method));
-    for (int32_t i = 0; i < n_windows; ++i) {
-        const mr_spans* s = spans[i];
-        if (!s || s->ctx != ctx || !a3[i] || !a3_valid[i]) return mr_fail(ctx, MR_ERR_ARG, "%s: bad window %d", who, i);
-        if (n_ops[i] < 0 || n_ops[i] > K)
-            return mr_fail(ctx, MR_ERR_ARG, "%s: n_ops[%d] = %d is not in 0..%d", who, i, n_ops[i], K);
-        for (int32_t j = 0; j < n_ops[i]; ++j) {
-            const int32_t c = podops[(size_t)i * K + j];
-            if (c < 0 || c >= s->n_podops)
-                return mr_fail(ctx, MR_ERR_ARG, "%s: window %d: podops[%d] = %d is no pod-op code of the table (%d)", who, i,
-                               j, c, s->n_podops);
-        }
-    }
+    MR_TRY(ev_check_windows(ctx, who, L, false));
     for (int32_t i = 0; i < n_windows; ++i) {
         if (!spans[i]->has_times) return mr_fail(ctx, MR_ERR_STATE, "%s: window %d needs startTime/endTime columns", who, i);
         if (what == MR_LAT_SELF && spans[i]->grow.p)
@@ -385,30 +356,14 @@ extern "C" int mr_windows_latency(mr_ctx* ctx, int32_t n_windows, const mr_spans
     std::fill(out, out + (size_t)n_windows * K * 2 * n_q, 0.0);
     std::fill(count, count + (size_t)n_windows * K * 2, (int64_t)0);
     std::fill(status, status + n_windows, (int32_t)MR_OK);
-    // the windows' detectors, one after another; each partition stays on the device.  Windows that
-    // give the same SLO arrays for the same number of ops share one upload.
-    struct Slo {
-        DBuf<double> a3;
-        DBuf<uint8_t> ok;
-    };
-    std::map<std::tuple<const double*, const uint8_t*, int32_t>, Slo> slos;
+    // the windows' detectors, one after another (mr_evidence.h); each partition stays on the device
+    EvSlos slos;
     std::vector<DBuf<uint8_t>> dst((size_t)n_windows);
     std::vector<LatReq> rq((size_t)n_windows);
     for (int32_t i = 0; i < n_windows; ++i) {
         const mr_spans* s = spans[i];
-        const int32_t NT = s->n_traces;
-        Slo& sl = slos[std::make_tuple(a3[i], a3_valid[i], s->n_svcops)];
-        if (!sl.a3.p) {
-            MR_TRY(sl.a3.upload(ctx, a3[i], (size_t)s->n_svcops));
-            MR_TRY(sl.ok.upload(ctx, a3_valid[i], (size_t)s->n_svcops));
-        }
-        MR_TRY(dst[(size_t)i].zero(ctx, (size_t)std::max(NT, 1)));
-        int32_t na = 0, nn = 0;
-        int64_t nin = 0;
-        const int rc = mr_detect_dev(ctx, s, t0[i], t1[i], sl.a3.p, sl.ok.p, dst[(size_t)i].p, &na, &nn, &nin);
-        const bool empty = rc == MR_ERR_VALUE && nin == 0;   // T2: "Current span list is empty"
-        if (rc != MR_OK && !empty) return rc;
-        if (empty) status[i] = MR_ERR_VALUE;
+        bool launched = false, empty = false;
+        MR_TRY(ev_partition(ctx, L, i, slos, dst[(size_t)i], nullptr, &launched, &empty, status));
         rq[(size_t)i] = LatReq{s, t0[i], t1[i], dst[(size_t)i].p, s->indexed && s->uniform_times,
                                podops + (size_t)i * K, empty ? 0 : n_ops[i]};
     }

@@ -44,16 +44,6 @@ static const bool g_debug = getenv("MR_DEBUG") != nullptr;
         }                                                                                                  \
     } while (0)
 
-inline int num_cus() {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            v = 256;
-        return std::max(v, 1);
-    }();
-    return ncu;
-}
-
 // an A/B and test knob that is on unless set to 0 (read per call: tests flip them)
 inline bool knob_on(const char* name) {
     const char* e = getenv(name);

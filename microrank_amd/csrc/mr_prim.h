@@ -26,6 +26,30 @@ __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
     return v;
 }
 
+// Runs of equal keys among a wave's consecutive lanes (rows of one parent, traces of one kind: mostly
+// adjacent, so an atomic per lane would serialise on one address).  Every lane of the wave brings
+// (key, v); v becomes the reduction of the lane's run up to and including the lane, and the return value
+// says that the lane is its run's last -- the one lane that holds the whole run and issues its atomics.
+// Head flags from the key one lane below, the run's index from a ballot of the heads, then a shuffle scan
+// that combines only inside a run.  V: `V up(int off) const`, the value `off` lanes below, and
+// `void merge(const V& lower)`; the merges are integer adds and maxima, so the order is free.
+template <class K, class V>
+__device__ __forceinline__ bool wave_run_reduce(int lane, K key, V& v) {
+    const K pk = __shfl_up(key, 1, WAVE);
+    const bool head = lane == 0 || pk != key;
+    const uint64_t heads = __ballot(head);
+    const int seg = __popcll(heads & (~0ull >> (63 - lane)));   // heads at or below this lane
+    V acc = v;   // (a local copy: its conditional merges compile to selects; through the reference, to branches)
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const V lower = acc.up(off);
+        const int so = __shfl_up(seg, off, WAVE);
+        if (lane >= off && so == seg) acc.merge(lower);
+    }
+    v = acc;
+    return ((heads >> 1) >> lane & 1ull) || lane == WAVE - 1;   // (the next lane heads a run)
+}
+
 // Block-wide reductions; every thread gets the result.  `red` must hold blockDim/64 doubles.
 __device__ __forceinline__ double block_sum(double v, double* red) {
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE, nw = blockDim.x / WAVE;

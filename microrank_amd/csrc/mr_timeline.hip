@@ -15,33 +15,21 @@
 //                csum, read only by rows that have a slot.  Blocks [rb, rb + tb) make the TRACE pass of
 //                slot -1: a lane per trace code, its state, start and end.  Both feed one reduction:
 //                key = (slot * (B + 2) + bucket) * 2 + side, buckets B and B + 1 standing for "before" and
-//                "after" the bucket range.  Runs of equal keys inside a wave are reduced by a segmented
-//                scan (a wave without a key skips it) and the run's last lane adds n, the uint64 sum and
-//                the maximum of the bias-flipped value (v ^ 2^63: order-preserving, and the zeroed counter
-//                is the smallest) to the block's table of TL_H entries in LDS (32 KB: key, n, sum, biased
-//                max), direct-mapped where the window's distinct asked * (B + 2) * 2 keys fit (the key
-//                array is then unused), else with mr_call_edges.hip's claim-a-slot hash, a key that finds
-//                its slot taken adding to the global counters itself.
-//                A block works through many tiles and adds its table to the window's dense counters once,
-//                at its end, with 64-bit integer atomics.  Integer adds and maxima are order-free: the
-//                counters are bitwise reproducible, whatever the cut and whichever path a run took
+//                "after" the bucket range.  Runs of equal keys inside a wave are reduced (mr_prim.h
+//                wave_run_reduce; a wave without a key skips it) and the run's last lane adds n, the sum
+//                and the maximum to the block's counter table in LDS (mr_evidence.h EvTable), direct-mapped
+//                where the window's distinct asked * (B + 2) * 2 keys fit, else hashed.  The block adds its
+//                table to the window's dense counters once, at its end.  The counters are bitwise
+//                reproducible, whatever the cut and whichever path a run took
 //   k_tl_finish  a thread per output word: the counters of the slot that answers an asked entry (a
 //                duplicate: its first appearance's), the maximum un-biased and 0 where the count is 0, the
 //                two outside buckets into tl_out
 // One row pass and one trace pass per chunk of windows -- never a launch per asked op or per bucket -- and
-// one pinned read-back per chunk, which carries the detectors' counts too (an empty window is found
-// there: its states are all 0, so its counters stayed 0): no host synchronisation per window.  Windows go
-// in chunks whose dense counters (K * (B + 2) * 2 * 3 words per window) stay under TL_SCRATCH_BYTES
-// (MR_TL_CHUNK, read per call, forces the windows per chunk; MR_TL_BLOCKS the blocks per window of each
-// pass: tests reach every cut at small sizes).
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <tuple>
-#include <vector>
-
-#include "mr_prim.h"
+// one pinned read-back per chunk, which carries the detectors' counts too: no host synchronisation per
+// window.  The window list's front end is mr_evidence.h's; a chunk's dense counters take K * (B + 2) * 2 * 3
+// words per window (MR_TL_CHUNK, read per call, forces the windows per chunk; MR_TL_BLOCKS the blocks
+// per window of each pass: tests reach every cut at small sizes).
+#include "mr_evidence.h"
 
 namespace {
 constexpr int TL_T = 256;                     // threads per block
@@ -49,11 +37,7 @@ constexpr int TL_U = 4;                       // k_tl_count: rows (traces) in fl
 constexpr int TL_TILE = TL_T * TL_U;          // rows of a block's tile
 constexpr int TL_MAXOPS = 64;                 // asked slots per window (the evidence entries' limit)
 constexpr int TL_MAXB = 512;                  // buckets
-constexpr int TL_HB = 10, TL_H = 1 << TL_HB;  // entries of a block's counter table in LDS
-constexpr size_t TL_SCRATCH_BYTES = (size_t)64 << 20;   // a chunk's dense counters
-constexpr int TL_MAX_Y = 32768;               // windows per launch (gridDim.y)
 constexpr int TL_MAX_CB = 4096;               // row blocks per window (grid-stride over the tiles)
-constexpr unsigned long long TL_BIAS = 1ull << 63;
 
 struct TlWin {
     const int32_t *podop, *trace;
@@ -78,63 +62,18 @@ __device__ __forceinline__ int tl_bucket(long long ts, long long b0, unsigned lo
     return b >= (unsigned long long)B ? B + 1 : (int)b;
 }
 
-__device__ __forceinline__ void tl_add(unsigned long long* cnt, int32_t kd, unsigned long long n, unsigned long long sum,
-                                       unsigned long long mx) {
-    unsigned long long* p = cnt + (size_t)kd * 3;
-    atomicAdd(p, n);
-    atomicAdd(p + 1, sum);
-    atomicMax(p + 2, mx);
-}
-
-// a run's sums into the block's table: entry kd where the table is direct-mapped, else the slot of kd's
-// hash, claimed by the first key that comes; a key that finds its slot taken by another goes to the global
-// counters itself (integer adds and maxima either way: the same bits)
-__device__ __forceinline__ void tl_add_block(bool direct, unsigned long long* hk, unsigned long long* hn,
-                                             unsigned long long* hs, unsigned long long* hm, unsigned long long* cnt,
-                                             int32_t kd, unsigned long long n, unsigned long long sum,
-                                             unsigned long long mx) {
-    uint32_t h = (uint32_t)kd;
-    if (!direct) {
-        h = (uint32_t)(((unsigned long long)kd * 0x9E3779B97F4A7C15ull) >> (64 - TL_HB));
-        const unsigned long long mine = (unsigned long long)kd + 1ull;
-        const unsigned long long prev = atomicCAS(&hk[h], 0ull, mine);
-        if (prev != 0ull && prev != mine) {
-            tl_add(cnt, kd, n, sum, mx);
-            return;
-        }
-    }
-    atomicAdd(&hn[h], n);
-    atomicAdd(&hs[h], sum);
-    atomicMax(&hm[h], mx);
-}
-
-// every lane of the wave brings (kd, v), kd < 0: nothing; runs of equal keys are reduced and added once
-__device__ __forceinline__ void tl_reduce(int lane, bool direct, unsigned long long* hk, unsigned long long* hn,
-                                          unsigned long long* hs, unsigned long long* hm, unsigned long long* cnt,
-                                          int32_t kd, unsigned long long d) {
+// every lane of the wave brings (kd, d), kd < 0: nothing; runs of equal keys are reduced and added once
+__device__ __forceinline__ void tl_reduce(int lane, bool direct, EvTable& tab, unsigned long long* cnt, int32_t kd,
+                                          unsigned long long d) {
     if (__ballot(kd >= 0) == 0ull) return;   // (wave-uniform)
-    unsigned long long n = kd >= 0 ? 1ull : 0ull, v = kd >= 0 ? d : 0ull, mx = kd >= 0 ? d ^ TL_BIAS : 0ull;
-    const int32_t pk = __shfl_up(kd, 1, WAVE);
-    const bool head = lane == 0 || pk != kd;
-    const uint64_t heads = __ballot(head);
-    const int seg = __popcll(heads & (~0ull >> (63 - lane)));   // heads at or below this lane
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const unsigned long long no = __shfl_up(n, off, WAVE), vo = __shfl_up(v, off, WAVE), mo = __shfl_up(mx, off, WAVE);
-        const int so = __shfl_up(seg, off, WAVE);
-        if (lane >= off && so == seg) {
-            n += no;
-            v += vo;
-            mx = mo > mx ? mo : mx;
-        }
-    }
-    const bool tail = ((heads >> 1) >> lane & 1ull) || lane == WAVE - 1;   // (the next lane heads a run)
-    if (kd >= 0 && tail) tl_add_block(direct, hk, hn, hs, hm, cnt, kd, n, v, mx);
+    EvRun run = ev_run_of(kd >= 0, d);
+    const bool tail = wave_run_reduce(lane, kd, run);
+    if (kd >= 0 && tail) tab.add(direct, cnt, kd, run);
 }
 
 // blocks [0, rb) of a window: the row pass; [rb, gridDim.x): the trace pass of slot -1
 __global__ void __launch_bounds__(TL_T) k_tl_count(const TlWin* __restrict__ ws, int32_t rb, int32_t B) {
-    __shared__ unsigned long long hk[TL_H], hn[TL_H], hs[TL_H], hm[TL_H];   // key + 1 (0: free; hashed only), n, sum, biased max
+    __shared__ EvTable tab;   // n, sum, biased max
     __shared__ int32_t ops[TL_MAXOPS];
     const TlWin& w = ws[blockIdx.y];
     const bool rows = (int32_t)blockIdx.x < rb;
@@ -144,7 +83,7 @@ __global__ void __launch_bounds__(TL_T) k_tl_count(const TlWin* __restrict__ ws,
     const int lane = threadIdx.x & (WAVE - 1);
     const bool direct = w.direct != 0;
     const int32_t n_ops = w.n_ops, BB = B + 2;
-    for (int i = threadIdx.x; i < TL_H; i += TL_T) hk[i] = hn[i] = hs[i] = hm[i] = 0ull;
+    tab.clear(threadIdx.x, TL_T);
     if (threadIdx.x < TL_MAXOPS) ops[threadIdx.x] = (int)threadIdx.x < n_ops ? w.op[threadIdx.x] : -1;
     __syncthreads();
     const uint32_t NT = (uint32_t)w.NT;
@@ -188,7 +127,7 @@ __global__ void __launch_bounds__(TL_T) k_tl_count(const TlWin* __restrict__ ws,
                         if (sc >= 0 && sc < n_codes) d -= csum[sc];
                     }
                 }
-                tl_reduce(lane, direct, hk, hn, hs, hm, w.cnt, kd, d);
+                tl_reduce(lane, direct, tab, w.cnt, kd, d);
             }
         }
     } else {
@@ -210,15 +149,12 @@ __global__ void __launch_bounds__(TL_T) k_tl_count(const TlWin* __restrict__ ws,
                     kd = (all * BB + tl_bucket(ts, b0, bw, B)) * 2 + (st[k] - 1);
                     d = (unsigned long long)w.tte[t] - (unsigned long long)ts;
                 }
-                tl_reduce(lane, direct, hk, hn, hs, hm, w.cnt, kd, d);
+                tl_reduce(lane, direct, tab, w.cnt, kd, d);
             }
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < TL_H; i += TL_T) {
-        if (direct ? hn[i] != 0ull : hk[i] != 0ull)
-            tl_add(w.cnt, direct ? i : (int32_t)(hk[i] - 1ull), hn[i], hs[i], hm[i]);
-    }
+    tab.flush<int32_t>(direct, w.cnt, threadIdx.x, TL_T);
 }
 
 // word e < n1 = cw * K * B * 2 (window, asked entry, bucket, side): its count, sum and maximum; word n1 + e2,
@@ -241,7 +177,7 @@ __global__ void __launch_bounds__(TL_T) k_tl_finish(const TlWin* __restrict__ ws
             const unsigned long long* p = ws[wi].cnt + (size_t)((u * BB + b) * 2 + side) * 3;
             c = (long long)p[0];
             s = (long long)p[1];
-            x = c ? (long long)(p[2] ^ TL_BIAS) : 0ll;
+            x = c ? (long long)(p[2] ^ EV_BIAS) : 0ll;
         }
         ocnt[e] = c;
         osum[e] = s;
@@ -255,21 +191,6 @@ __global__ void __launch_bounds__(TL_T) k_tl_finish(const TlWin* __restrict__ ws
         oout[e2] = u >= 0 ? (long long)ws[wi].cnt[(size_t)((u * BB + B + which) * 2 + side) * 3] : 0ll;
     }
 }
-
-int tl_num_cus() {
-    static const int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            v = 256;
-        return std::max(v, 1);
-    }();
-    return ncu;
-}
-
-int tl_env(const char* name) {   // (test knobs, read per call; 0: not set)
-    const char* e = getenv(name);
-    return e ? std::max(atoi(e), 0) : 0;
-}
 }  // namespace
 
 extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
@@ -278,27 +199,14 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
                                    const int64_t* bw, int32_t B, int64_t* tl_cnt, int64_t* tl_sum, int64_t* tl_max,
                                    int64_t* tl_out, int32_t* status) {
     const char* who = "mr_windows_timeline";
-    if (!ctx || n_windows < 0 ||
-        (n_windows && (!spans || !t0 || !t1 || !a3 || !a3_valid || !podops || !n_ops || !b0 || !bw || !tl_cnt || !tl_sum ||
-                       !tl_max || !tl_out || !status)))
-        return mr_fail(ctx, MR_ERR_ARG, "%s: bad arguments", who);
-    if (K < 1 || K > TL_MAXOPS) return mr_fail(ctx, MR_ERR_ARG, "%s: K = %d is not in 1..%d", who, K, TL_MAXOPS);
+    const EvList L{n_windows, spans, t0, t1, a3, a3_valid, podops, n_ops, K};
+    MR_TRY(ev_check_args(ctx, who, L, !n_windows || (b0 && bw && tl_cnt && tl_sum && tl_max && tl_out && status), TL_MAXOPS));
     if (B < 1 || B > TL_MAXB) return mr_fail(ctx, MR_ERR_ARG, "%s: B = %d is not in 1..%d", who, B, TL_MAXB);
     if (what != MR_LAT_DURATION && what != MR_LAT_SELF) return mr_fail(ctx, MR_ERR_ARG, "%s: unknown what %d", who, what);
-    for (int32_t i = 0; i < n_windows; ++i) {
-        const mr_spans* s = spans[i];
-        if (!s || s->ctx != ctx || !a3[i] || !a3_valid[i]) return mr_fail(ctx, MR_ERR_ARG, "%s: bad window %d", who, i);
-        if (bw[i] <= 0)
-            return mr_fail(ctx, MR_ERR_ARG, "%s: window %d: the bucket width %lld is not positive", who, i, (long long)bw[i]);
-        if (n_ops[i] < 0 || n_ops[i] > K)
-            return mr_fail(ctx, MR_ERR_ARG, "%s: n_ops[%d] = %d is not in 0..%d", who, i, n_ops[i], K);
-        for (int32_t j = 0; j < n_ops[i]; ++j) {
-            const int32_t c = podops[(size_t)i * K + j];
-            if (c < -1 || c >= s->n_podops)
-                return mr_fail(ctx, MR_ERR_ARG, "%s: window %d: podops[%d] = %d is neither -1 nor a pod-op code of the table (%d)",
-                               who, i, j, c, s->n_podops);
-        }
-    }
+    MR_TRY(ev_check_windows(ctx, who, L, true, [&](int32_t i) {
+        return bw[i] > 0 ? MR_OK
+                         : mr_fail(ctx, MR_ERR_ARG, "%s: window %d: the bucket width %lld is not positive", who, i, (long long)bw[i]);
+    }));
     for (int32_t i = 0; i < n_windows; ++i) {
         const mr_spans* s = spans[i];
         bool all = false;
@@ -327,31 +235,23 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
     std::fill(tl_out, tl_out + (size_t)n_windows * R2, (int64_t)0);
     std::fill(status, status + n_windows, (int32_t)MR_OK);
     hipStream_t st = ctx->stream;
-    const int forced_chunk = tl_env("MR_TL_CHUNK"), forced_blocks = tl_env("MR_TL_BLOCKS");
+    const int forced_chunk = knob_int("MR_TL_CHUNK"), forced_blocks = knob_int("MR_TL_BLOCKS");
     const int32_t BB = B + 2;
     const size_t wds = (size_t)K * BB * 2 * 3;   // dense counter words of a window
-    // Windows that give the same SLO arrays for the same number of ops share one upload (the call's).
-    struct Slo {
-        DBuf<double> a3;
-        DBuf<uint8_t> ok;
-    };
-    std::map<std::tuple<const double*, const uint8_t*, int32_t>, Slo> slos;
+    EvSlos slos;
     for (int32_t c0 = 0; c0 < n_windows;) {
-        // the chunk: consecutive windows while their dense counters fit the scratch (at least one)
-        int32_t c1 = c0 + 1;
-        while (c1 < n_windows && c1 - c0 < TL_MAX_Y &&
-               (forced_chunk ? c1 - c0 < forced_chunk : (size_t)(c1 - c0 + 1) * wds * 8 <= TL_SCRATCH_BYTES))
-            ++c1;
+        size_t words = 0;
+        const int32_t c1 = ev_chunk_end(c0, n_windows, forced_chunk, 8, [&](int32_t) { return wds; }, &words);
         const int32_t cw = c1 - c0;
         const size_t n1 = (size_t)cw * R1, n2 = (size_t)cw * R2;
         std::vector<DBuf<uint8_t>> dstate((size_t)cw);
         std::vector<TlWin> hw((size_t)cw);
         std::vector<int32_t> rep((size_t)cw * K, -1);   // the slot that answers asked entry j (a duplicate: its first appearance's)
         DBuf<unsigned long long> cnt, ob;
-        MR_TRY(cnt.zero(ctx, (size_t)cw * wds));
+        MR_TRY(cnt.zero(ctx, words));
         // ob, the chunk's ONE read-back: [cw * DW] the detectors' counter shards (u64), then as int64 [n1] counts,
         // [n1] sums, [n1] maxima, [n2] the outside counts
-        constexpr size_t DW = 3 * MR_DETECT_SHARDS;
+        constexpr size_t DW = EV_DW;
         const size_t ob_words = (size_t)cw * DW + 3 * n1 + n2;
         MR_TRY(ob.zero(ctx, ob_words));
         std::vector<char> det_async((size_t)cw, 0);
@@ -361,28 +261,11 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
             const int32_t gi = c0 + i;
             const mr_spans* s = spans[gi];
             const int32_t NT = s->n_traces;
-            Slo& sl = slos[std::make_tuple(a3[gi], a3_valid[gi], s->n_svcops)];
-            if (!sl.a3.p) {
-                MR_TRY(sl.a3.upload(ctx, a3[gi], (size_t)s->n_svcops));
-                MR_TRY(sl.ok.upload(ctx, a3_valid[gi], (size_t)s->n_svcops));
-            }
-            MR_TRY(dstate[(size_t)i].zero(ctx, (size_t)std::max(NT, 1)));
-            bool empty = false;
-            if (s->indexed && s->uniform_times) {
-                // the per-trace detector, launched only: its counts come back with the chunk's read-back (an
-                // empty window's states are all 0, so its counters stay 0 whatever is asked)
-                MR_TRY(mr_detect_indexed_launch(ctx, s, t0[gi], t1[gi], sl.a3.p, sl.ok.p, dstate[(size_t)i].p,
-                                                ob.p + (size_t)i * DW));
-                det_async[(size_t)i] = 1;
-                ++n_async;
-            } else {   // (a table without rows: the row-level detector, which reads its sizes back)
-                int32_t na = 0, nn = 0;
-                int64_t nin = 0;
-                const int rc = mr_detect_dev(ctx, s, t0[gi], t1[gi], sl.a3.p, sl.ok.p, dstate[(size_t)i].p, &na, &nn, &nin);
-                empty = rc == MR_ERR_VALUE && nin == 0;   // T2: "Current span list is empty"
-                if (rc != MR_OK && !empty) return rc;
-                if (empty) status[gi] = MR_ERR_VALUE;
-            }
+            // (a table without rows goes through the row-level detector)
+            bool launched = false, empty = false;
+            MR_TRY(ev_partition(ctx, L, gi, slos, dstate[(size_t)i], ob.p + (size_t)i * DW, &launched, &empty, status));
+            det_async[(size_t)i] = launched;
+            n_async += launched;
             TlWin& w = hw[(size_t)i];
             memset(&w, 0, sizeof w);
             w.podop = s->podop.p;
@@ -398,20 +281,10 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
             w.bw = (unsigned long long)bw[gi];
             w.NT = NT;
             w.all_slot = -1;
-            int32_t n_row_ops = 0;
-            for (int32_t j = 0; j < (empty || NT == 0 || s->S == 0 || !s->indexed ? 0 : n_ops[gi]); ++j) {
-                const int32_t c = podops[(size_t)gi * K + j];
-                int32_t u = 0;
-                while (u < w.n_ops && w.op[u] != c) ++u;
-                if (u == w.n_ops) {
-                    w.op[w.n_ops++] = c;
-                    if (c < 0) w.all_slot = u;
-                    else ++n_row_ops;
-                }
-                rep[(size_t)i * K + j] = u;
-            }
-            w.direct = (int64_t)w.n_ops * BB * 2 <= TL_H;
-            if (n_row_ops) {
+            if (!(empty || NT == 0 || s->S == 0 || !s->indexed))
+                ev_slots(podops + (size_t)gi * K, n_ops[gi], w.op, &w.n_ops, &w.all_slot, &rep[(size_t)i * K]);
+            w.direct = (int64_t)w.n_ops * BB * 2 <= EV_H;
+            if (w.n_ops - (w.all_slot >= 0)) {   // (a pod-op is asked)
                 if (what == MR_LAT_SELF) {
                     MR_TRY(lat_csum_ensure(ctx, s));
                     w.csum = s->csum.p;
@@ -433,7 +306,7 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
             // a block keeps its counters in LDS over all its tiles and adds them to the window's once: few
             // blocks per window where the chunk's windows fill the device anyway
             const int64_t rtiles = cdiv(maxS, TL_TILE), ttiles = cdiv(maxNT, TL_TILE);
-            const int64_t per = std::max<int64_t>(1, 8 * (int64_t)tl_num_cus() / cw);
+            const int64_t per = ev_block_cap(8, cw);
             const int64_t rb = forced_blocks ? std::min<int64_t>(forced_blocks, rtiles)
                                              : std::min<int64_t>(rtiles, std::min<int64_t>(TL_MAX_CB, per));
             const int64_t tb = forced_blocks ? std::min<int64_t>(forced_blocks, ttiles)
@@ -448,23 +321,8 @@ extern "C" int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_span
             MR_TRY_HIP(ctx, hipGetLastError());
         }
         if (n_asked > 0 || n_async > 0) {
-            if (ctx->pin_ex_n < ob_words) {
-                if (ctx->pin_ex) (void)hipHostFree(ctx->pin_ex);
-                ctx->pin_ex = nullptr;
-                ctx->pin_ex_n = 0;
-                if (hipHostMalloc((void**)&ctx->pin_ex, ob_words * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-                    return mr_fail(ctx, MR_ERR_OOM, "%s: pinned read-back words", who);
-                ctx->pin_ex_n = ob_words;
-            }
-            MR_TRY_HIP(ctx, hipMemcpyAsync(ctx->pin_ex, ob.p, ob_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            MR_TRY_HIP(ctx, hipStreamSynchronize(st));
-            for (int32_t i = 0; i < cw; ++i) {
-                if (!det_async[(size_t)i]) continue;
-                int32_t na = 0, nn = 0;
-                int64_t nin = 0;
-                mr_detect_sum(ctx->pin_ex + (size_t)i * DW, &na, &nn, &nin);
-                if (nin == 0) status[c0 + i] = MR_ERR_VALUE;   // T2: "Current span list is empty"
-            }
+            MR_TRY(mr_pin_ex(ctx, ob.p, ob_words, who));
+            ev_launched_status(ctx->pin_ex, det_async, c0, status);
             if (n_asked > 0) {
                 const int64_t* h = (const int64_t*)(ctx->pin_ex + (size_t)cw * DW);
                 memcpy(tl_cnt + (size_t)c0 * R1, h, n1 * sizeof(int64_t));

@@ -905,26 +905,13 @@ def op_latency(data, start_time, end_time, slo, ops, *, q=(0.5, 0.99), what="sel
     return res
 
 
-def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="linear"):
-    """op_latency's evidence for many windows in one call (mr_windows_latency: one sort for all of
-    them).  ``windows`` as rank_windows'; ``ops`` one array of pod-op codes per window -- the first
-    element of rank_windows' tuples.  Returns per window {code: (normal[n_q], abnormal[n_q], n_normal,
-    n_abnormal)} in raw duration units (rank_windows works in codes; names and rounding are the
-    callers'); each window's partition is its own detector's, computed on the device.  An empty
-    window (rank_windows' status MR_ERR_VALUE) answers zeros."""
-    qv, wcode, mcode = _latency_args(q, what, method)
+def _window_args(windows):
+    """``windows`` (rank_windows' tuples) as the leading arguments of the library's evidence entries:
+    (keep, spans, t0, t1, a3, ok).  a3 / ok point into ``keep``, the contiguous SLO arrays, which must
+    outlive the call; windows that share their SLO array objects give the library one pointer: one upload."""
     n = len(windows)
-    if len(ops) != n:
-        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
-    if n == 0:
-        return []
-    ops = [np.ascontiguousarray(o, np.int32).reshape(-1) for o in ops]
-    k = max(max(o.size for o in ops), 1)
-    if k > 64:
-        raise ValueError(f"a window asks {k} ops; at most 64")
     keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
            [np.ascontiguousarray(w[4], np.uint8) for w in windows]
-    # (windows that share their SLO arrays give the library one pointer: one upload)
     addr = {}
     for i, w in enumerate(windows):
         for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
@@ -934,10 +921,39 @@ def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="li
     t1 = np.array([int(w[2]) for w in windows], np.int64)
     a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
     ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
+    return keep, spans, t0, t1, a3, ok
+
+
+def _asked_args(ops, n, none_ok=False):
+    """``ops``, one sequence of pod-op codes per window (none_ok: None allowed, passed as -1), as (asked, k,
+    cod, n_ops): the codes as Python lists, the widest list's length (at least 1), the (n, k) int32 codes
+    and the n list lengths.  ValueError unless there are n lists of at most 64 codes."""
+    if len(ops) != n:
+        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
+    asked = [[None if none_ok and o is None else int(o) for o in lst] for lst in ops]
+    k = max([len(a) for a in asked] + [1])
+    if k > 64:
+        raise ValueError(f"a window asks {k} ops; at most 64")
     cod = np.zeros((n, k), np.int32)
-    n_ops = np.array([o.size for o in ops], np.int32)
-    for i, o in enumerate(ops):
-        cod[i, :o.size] = o
+    n_ops = np.array([len(a) for a in asked], np.int32)
+    for i, a in enumerate(asked):
+        cod[i, :len(a)] = [-1 if c is None else c for c in a]
+    return asked, k, cod, n_ops
+
+
+def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="linear"):
+    """op_latency's evidence for many windows in one call (mr_windows_latency: one sort for all of
+    them).  ``windows`` as rank_windows'; ``ops`` one array of pod-op codes per window -- the first
+    element of rank_windows' tuples.  Returns per window {code: (normal[n_q], abnormal[n_q], n_normal,
+    n_abnormal)} in raw duration units (rank_windows works in codes; names and rounding are the
+    callers'); each window's partition is its own detector's, computed on the device.  An empty
+    window (rank_windows' status MR_ERR_VALUE) answers zeros."""
+    qv, wcode, mcode = _latency_args(q, what, method)
+    n = len(windows)
+    asked, k, cod, n_ops = _asked_args([np.ascontiguousarray(o, np.int32).reshape(-1) for o in ops], n)
+    if n == 0:
+        return []
+    keep, spans, t0, t1, a3, ok = _window_args(windows)
     out = np.zeros((n, k, 2, qv.size), np.float64)
     cnt = np.zeros((n, k, 2), np.int64)
     status = np.zeros(n, np.int32)
@@ -945,8 +961,8 @@ def windows_latency(ctx, windows, ops, *, q=(0.5, 0.99), what="self", method="li
                                              ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, wcode, ptr(qv, C.c_double),
                                              qv.size, mcode, ptr(out, C.c_double), ptr(cnt, C.c_int64),
                                              ptr(status, C.c_int32)), "mr_windows_latency")
-    return [{int(c): (out[i, j, 0].copy(), out[i, j, 1].copy(), int(cnt[i, j, 0]), int(cnt[i, j, 1]))
-             for j, c in enumerate(ops[i])} for i in range(n)]
+    return [{c: (out[i, j, 0].copy(), out[i, j, 1].copy(), int(cnt[i, j, 0]), int(cnt[i, j, 1]))
+             for j, c in enumerate(asked[i])} for i in range(n)]
 
 
 def windows_kind_breakdown(ctx, windows, ops, *, m=8):
@@ -965,30 +981,10 @@ def windows_kind_breakdown(ctx, windows, ops, *, m=8):
     a layout order are not covered (RuntimeError from the library)."""
     m = _kind_m(m)
     n = len(windows)
-    if len(ops) != n:
-        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
-    asked = [[None if o is None else int(o) for o in lst] for lst in ops]
-    k = max([len(a) for a in asked] + [1])
-    if k > 64:
-        raise ValueError(f"a window asks {k} ops; at most 64")
+    asked, k, cod, n_ops = _asked_args(ops, n, none_ok=True)
     if n == 0:
         return []
-    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
-           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
-    # (windows that share their SLO arrays give the library one pointer: one upload)
-    addr = {}
-    for i, w in enumerate(windows):
-        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
-            addr.setdefault(id(src), a.ctypes.data)
-    spans = (_lib.P * n)(*[w[0].h for w in windows])
-    t0 = np.array([int(w[1]) for w in windows], np.int64)
-    t1 = np.array([int(w[2]) for w in windows], np.int64)
-    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
-    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
-    cod = np.zeros((n, k), np.int32)
-    n_ops = np.array([len(a) for a in asked], np.int32)
-    for i, a in enumerate(asked):
-        cod[i, :len(a)] = [-1 if c is None else c for c in a]
+    keep, spans, t0, t1, a3, ok = _window_args(windows)
     col = [np.zeros((n, k, m), np.int32) for _ in range(5)]
     cnt, kinds = np.zeros((n, k), np.int32), np.zeros((n, k), np.int32)
     tot = np.zeros((n, k, 2), np.int64)
@@ -1041,30 +1037,10 @@ def windows_call_edges(ctx, windows, ops, *, m=8):
     library)."""
     m = _call_m(m)
     n = len(windows)
-    if len(ops) != n:
-        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
-    asked = [[int(o) for o in lst] for lst in ops]
-    k = max([len(a) for a in asked] + [1])
-    if k > 64:
-        raise ValueError(f"a window asks {k} ops; at most 64")
+    asked, k, cod, n_ops = _asked_args(ops, n)
     if n == 0:
         return []
-    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
-           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
-    # (windows that share their SLO arrays give the library one pointer: one upload)
-    addr = {}
-    for i, w in enumerate(windows):
-        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
-            addr.setdefault(id(src), a.ctypes.data)
-    spans = (_lib.P * n)(*[w[0].h for w in windows])
-    t0 = np.array([int(w[1]) for w in windows], np.int64)
-    t1 = np.array([int(w[2]) for w in windows], np.int64)
-    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
-    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
-    cod = np.zeros((n, k), np.int32)
-    n_ops = np.array([len(a) for a in asked], np.int32)
-    for i, a in enumerate(asked):
-        cod[i, :len(a)] = a
+    keep, spans, t0, t1, a3, ok = _window_args(windows)
     peer = np.zeros((n, k, 2, m), np.int32)
     calls, dsum, dmax = (np.zeros((n, k, 2, m, 2), np.int64) for _ in range(3))
     cnt, peers = np.zeros((n, k, 2), np.int32), np.zeros((n, k, 2), np.int32)
@@ -1136,38 +1112,18 @@ def windows_timeline(ctx, windows, ops, *, buckets=30, what="self", origin=None,
     trace shard are not covered (RuntimeError from the library)."""
     b, wcode = _timeline_args(buckets, what)
     n = len(windows)
-    if len(ops) != n:
-        raise ValueError(f"ops holds {len(ops)} lists for {n} windows")
-    asked = [[int(o) for o in lst] for lst in ops]
-    k = max([len(a) for a in asked] + [1])
-    if k > 64:
-        raise ValueError(f"a window asks {k} ops; at most 64")
+    asked, k, cod, n_ops = _asked_args(ops, n)
     if n == 0:
         return []
-    t0 = np.array([int(w[1]) for w in windows], np.int64)
-    t1 = np.array([int(w[2]) for w in windows], np.int64)
-    whole = [int(a) == _lib.INT64_MIN and int(z) == _lib.INT64_MAX for a, z in zip(t0, t1)]
-    if (origin is None or width is None) and any(whole):
+    ends = [(int(w[1]), int(w[2])) for w in windows]
+    if (origin is None or width is None) and (_lib.INT64_MIN, _lib.INT64_MAX) in ends:
         raise ValueError("a whole-table window has no default buckets: give origin and width")
-    org = _per_window(origin, n, "origin") if origin is not None else [int(a) for a in t0]
-    wid = _per_window(width, n, "width") if width is not None else [(int(z) - int(a)) // b + 1 for a, z in zip(t0, t1)]
+    org = _per_window(origin, n, "origin") if origin is not None else [a for a, _ in ends]
+    wid = _per_window(width, n, "width") if width is not None else [(z - a) // b + 1 for a, z in ends]
     if any(x <= 0 for x in wid):
         raise ValueError(f"a bucket width must be positive, not {min(wid)}")
     b0, bw = np.array(org, np.int64), np.array(wid, np.int64)
-    keep = [np.ascontiguousarray(w[3], np.float64) for w in windows] + \
-           [np.ascontiguousarray(w[4], np.uint8) for w in windows]
-    # (windows that share their SLO arrays give the library one pointer: one upload)
-    addr = {}
-    for i, w in enumerate(windows):
-        for src, a in ((w[3], keep[i]), (w[4], keep[n + i])):
-            addr.setdefault(id(src), a.ctypes.data)
-    spans = (_lib.P * n)(*[w[0].h for w in windows])
-    a3 = (C.c_void_p * n)(*[addr[id(w[3])] for w in windows])
-    ok = (C.c_void_p * n)(*[addr[id(w[4])] for w in windows])
-    cod = np.zeros((n, k), np.int32)
-    n_ops = np.array([len(a) for a in asked], np.int32)
-    for i, a in enumerate(asked):
-        cod[i, :len(a)] = a
+    keep, spans, t0, t1, a3, ok = _window_args(windows)   # (behind the checks: they need no table)
     cnt, tot, mx = (np.zeros((n, k, b, 2), np.int64) for _ in range(3))
     out = np.zeros((n, k, 2, 2), np.int64)
     status = np.zeros(n, np.int32)

@@ -15,9 +15,19 @@ waits for):
       pod-op 4, id_rows 4, the parent row's trace 4, state 1 and pod-op 4 (the binary search in the edge
       dictionary stays in cache and is not counted).
 
+  (e) one windows_latency call (q = 0.5 and 0.99, self time) and one windows_timeline call (30 buckets, self
+      time) over the N windows: each top list.
+
 The GPU work runs in one child process under `timeout`; the parent never opens the GPU.
 
     python3 scripts/call_edges_cost.py [--windows 256] [--out profiles/call_edges.json]
+
+--parent-lib PATH (another build of libmicrorank_hip.so: the commit before) answers "did the code get slower"
+for a change that is meant to leave the timings alone: four child processes, the library chosen by
+MR_LIB_PATH, alternating parent, this tree, parent, this tree, each under `timeout`; the first one that fails
+ends the run.  Per timed entry the mean of this tree's two medians against the larger of the parent's two
+times 1.03 (DESIGN §4's box-to-box spread); the parent's own two medians say how far one build moves between
+processes.  The result goes to profiles/evidence_front.json.
 """
 import argparse
 import json
@@ -33,6 +43,8 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
 from converge_cost import Events  # noqa: E402  (scripts/ is sys.path[0])
 
 CALLS, WARMUP, M = 7, 2, 8
+TIMED = ("ranking_step", "kind_breakdown", "call_edges", "latency", "timeline")
+SPREAD = 1.03
 
 
 def summary(v):
@@ -45,7 +57,8 @@ def child(a):
 
     import bench
     from microrank_amd import _lib
-    from microrank_amd.online_rca import rank_windows, windows_call_edges, windows_kind_breakdown
+    from microrank_amd.online_rca import (rank_windows, windows_call_edges, windows_kind_breakdown, windows_latency,
+                                          windows_timeline)
     from microrank_amd.preprocess_data import DeviceSpans
 
     tabs = bench.c2_window_stream(a.windows, a.ops, a.traces, 0)   # (the generators fork before the GPU is touched)
@@ -61,7 +74,7 @@ def child(a):
         d.table = None   # (the host columns are slab views the next tables overwrite)
         wins.append((d, t0, t0 + 5 * 60 * 10**9, a3, ok))
     ev = Events(lib.mr_ctx_stream(ctx.h))
-    res = {"windows": len(wins), "ops": a.ops, "traces": a.traces, "calls": CALLS, "warmup": WARMUP, "m": M,
+    res = {"lib": a.child, "windows": len(wins), "ops": a.ops, "traces": a.traces, "calls": CALLS, "warmup": WARMUP, "m": M,
            "rows_per_window": [min(rows), statistics.median(rows), max(rows)]}
 
     def timed(fn):
@@ -78,6 +91,8 @@ def child(a):
     res["asked_per_window"] = [min(len(t) for t in tops), max(len(t) for t in tops)]
     res["kind_breakdown"] = timed(lambda: windows_kind_breakdown(ctx, wins, [[None] + t.tolist() for t in tops], m=M))
     res["call_edges"] = timed(lambda: keep.__setitem__("c", windows_call_edges(ctx, wins, tops, m=M)))
+    res["latency"] = timed(lambda: windows_latency(ctx, wins, tops, q=(0.5, 0.99), what="self"))
+    res["timeline"] = timed(lambda: windows_timeline(ctx, wins, tops, buckets=30, what="self"))
     listed = [sum(len(side[0]) for v in w.values() for side in v) for w in keep["c"]]
     res["listed_edges_per_window"] = [min(listed), max(listed)]
     res["calls_per_window_abn_nor"] = [[sum(v[1][2][k] for v in w.values()) for k in (0, 1)] for w in keep["c"][:4]]
@@ -93,28 +108,68 @@ def child(a):
     print("RESULT " + json.dumps(res), flush=True)
 
 
+def run_child(a, role, libpath):
+    """One child process under `timeout`: its RESULT line, or None when the step failed."""
+    env = dict(os.environ)
+    env.pop("MR_LIB_PATH", None)
+    if libpath:
+        env["MR_LIB_PATH"] = os.path.abspath(libpath)
+    cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", role,
+           "--windows", str(a.windows), "--ops", str(a.ops), "--traces", str(a.traces)]
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+    if p.returncode != 0 or not line:
+        print(f"the GPU step ({role}) failed (exit status {p.returncode})", flush=True)
+        return None
+    return json.loads(line[-1][len("RESULT "):])
+
+
+def compare(steps):
+    """Per timed entry: the four medians by HIP events and whether this tree keeps the parent's time."""
+    out = {}
+    for what in TIMED:
+        old = [s[what]["event_ms_median"] for s in steps if s["lib"] == "parent"]
+        new = [s[what]["event_ms_median"] for s in steps if s["lib"] == "new"]
+        bar = max(old) * SPREAD
+        out[what] = {"parent_ms": old, "new_ms": new, "new_mean_ms": statistics.mean(new), "bar_ms": bar,
+                     "within_bar": statistics.mean(new) <= bar, "parent_spread": max(old) / min(old),
+                     "parent_moved_more_than_bar": max(old) / min(old) > SPREAD}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=256)
     ap.add_argument("--ops", type=int, default=1000)
     ap.add_argument("--traces", type=int, default=200_000)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "call_edges.json"))
+    ap.add_argument("--parent-lib", default=None, help="another build of libmicrorank_hip.so: compare against it")
+    ap.add_argument("--out", default=None, help="default: profiles/call_edges.json, with --parent-lib profiles/evidence_front.json")
     ap.add_argument("--step-timeout", type=int, default=840)
-    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--child", default=None, help="(internal) run the GPU step; the value names the library")
     a = ap.parse_args()
     if a.child:
         return child(a)
-    cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child",
-           "--windows", str(a.windows), "--ops", str(a.ops), "--traces", str(a.traces)]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-    if p.returncode != 0 or not line:
-        sys.exit(f"the GPU step failed (exit status {p.returncode})")
-    res = json.loads(line[-1][len("RESULT "):])
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    out = a.out or os.path.join(REPO, "profiles", "evidence_front.json" if a.parent_lib else "call_edges.json")
+    if a.parent_lib:
+        steps = []
+        for role in ("parent", "new", "parent", "new"):
+            r = run_child(a, role, a.parent_lib if role == "parent" else None)
+            if r is None:   # nothing more on the GPU after a step that failed
+                sys.exit(1)
+            print(json.dumps({k: r[k]["event_ms_median"] for k in TIMED} | {"lib": role}), flush=True)
+            steps.append(r)
+        res = {"windows": a.windows, "ops": a.ops, "traces": a.traces, "calls": CALLS, "warmup": WARMUP, "m": M,
+               "spread": SPREAD, "entries": compare(steps), "steps": steps}
+        shown = res["entries"]
+    else:
+        res = shown = run_child(a, "new", None)
+        if res is None:
+            sys.exit(1)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
-    print(json.dumps(res, indent=1))
+        f.write("\n")
+    print(json.dumps(shown, indent=1))
 
 
 if __name__ == "__main__":
