@@ -693,6 +693,64 @@ int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* s
                         int64_t* tl_out /*[n_windows * K * 2 * 2]: window, slot, side, {before, after}*/,
                         int32_t* status /*[n_windows]*/);
 
+/* ------------------------------------------------------------------ replica evidence
+ * Is it this POD, or is it the OPERATION?  The ranking names pod-ops (podName_op); the detector and the SLO
+ * speak in service-ops (serviceName_op).  For each asked pod-op this entry answers with the pod-ops that
+ * share its service-op -- its replicas -- on each side of the window's detector partition: one replica
+ * slow and the others fine is a pod to drain; every replica slow on the abnormal traces is the operation.
+ * No reference counterpart.
+ * The table's map: sv(p) is the service-op code on the table's rows whose pod-op is p, over ALL rows of the
+ * table (not a window's); a pod-op without a row has sv(p) = -1; a pod-op whose rows carry two different
+ * service-op codes makes the table ambiguous (MR_ERR_STATE).  The replicas of service-op s are R(s) =
+ * { q : sv(q) == s }, in code order.  The map is built at the first call on a table and kept with it.
+ * Window, partition, sides and the selected rows are exactly mr_windows_timeline's op slots: window i =
+ * spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i]; its own mr_detect state, computed on the device and never
+ * copied out; side 0 normal, side 1 abnormal; the selected rows of (q, side) have podop == q, their trace in
+ * state side + 1, and lie inside the window; t0 == INT64_MIN and t1 == INT64_MAX: the whole table.  A row's
+ * value is duration (MR_LAT_DURATION) or duration - csum[span] (MR_LAT_SELF, csum as in mr_op_latency):
+ * int64 that wraps, possibly negative.
+ * Per asked entry p = podops[i * K + j], j < n_ops[i], s = sv(p); for every q in R(s) and side: cnt the
+ * selected rows, sum their values (int64 that wraps), max their largest value (0 where cnt is 0).  A replica
+ * is LIVE when cnt[0] + cnt[1] > 0.  The live replicas are ordered by abnormal count descending, then normal
+ * count ascending, then code ascending (mr_windows_call_edges' rule: a total order).
+ * Outputs, window i, asked entry j (x = i * K + j):
+ *   rp_pod[x * m + e]                       the first min(m, live) replicas, -1 padded; p is a replica like any other
+ *   rp_cnt / rp_sum / rp_max[(x * m + e) * 2 + side]   their numbers, 0 padded
+ *   rp_n[x]      the number of entries
+ *   rp_live[x]   the live replicas
+ *   rp_all[x]    |R(s)|, the replicas the table knows
+ *   rp_place[x]  the 0-based place of p among ALL live replicas under the order: -1 when p has no selected
+ *                row; it can be >= m
+ *   rp_own[(x * 2 + side) * 3 + {cnt, sum, max}]   the numbers of p itself, listed or not
+ *   rp_tot[(x * 2 + side) * 3 + {cnt, sum, max}]   the numbers over ALL live replicas: the service-op's own
+ *   status[i]    MR_OK, or MR_ERR_VALUE for an empty window (T2), whose outputs are the padding
+ * The padding: rp_pod -1, rp_place -1, everything else 0 (rp_all too).  A code asked twice is answered each
+ * time; two asked codes with the same sv get the same list and totals with their own rp_place and rp_own;
+ * sv(p) == -1 answers the padding; entries j >= n_ops[i] answer the padding.
+ * Every output is an integer sum, an integer maximum or a place in a total order, so the answer is the same
+ * bits under any cut into blocks, any chunking of the call's windows, any place of a window in the call and
+ * any neighbours: it is bitwise reproducible.  The order compares the two counts as they are (no packed
+ * key), so it is exact for every count a table can hold.
+ * MR_ERR_ARG: a null pointer, K outside 1..64, m outside 1..32, n_ops[i] outside 0..K, a code outside
+ * [0, n_podops), an unknown what, a table of another context.
+ * MR_ERR_STATE, tested in this order, the message naming which: a table without startTime / endTime columns;
+ * a time window on a table without trace-level times (the whole table is allowed there); MR_LAT_SELF on a
+ * trace shard of a larger table (cols.row set: children may lie on another rank); an ambiguous table (the
+ * message gives one offending pod-op code and its two service-op codes); a window whose asked service-ops
+ * hold 2^30 or more replicas (a counter's key has 31 bits).  There is no fallback for any of them.
+ * MR_LAT_DURATION on a shard is allowed: it covers THAT RANK's rows and that rank's map, as the timeline's op
+ * slots do; nothing merges the ranks' replicas.
+ * An argument error or a state error leaves the context usable. */
+int mr_windows_replicas(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                        const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                        const int32_t* podops /*[n_windows * K]*/, const int32_t* n_ops, int32_t K /*1..64*/,
+                        int32_t m /*1..32*/, int what /*MR_LAT_DURATION | MR_LAT_SELF*/,
+                        int32_t* rp_pod /*[n_windows * K * m]*/, int64_t* rp_cnt, int64_t* rp_sum,
+                        int64_t* rp_max /*[n_windows * K * m * 2]: window, entry, replica, side*/,
+                        int32_t* rp_n, int32_t* rp_live, int32_t* rp_all, int32_t* rp_place /*[n_windows * K]*/,
+                        int64_t* rp_own, int64_t* rp_tot /*[n_windows * K * 2 * 3]: window, entry, side, {cnt, sum, max}*/,
+                        int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

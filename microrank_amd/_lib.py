@@ -147,6 +147,10 @@ SIGNATURES = {
     "mr_windows_timeline": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, i64p, i64p, C.c_int32, i64p,
                                       i64p, i64p, i64p, i32p]),
+    # replica evidence: many windows' replicas (the pod-ops of the same service-op) per asked pod-op, both sides
+    "mr_windows_replicas": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, C.c_int, i32p, i64p, i64p,
+                                      i64p, i32p, i32p, i32p, i32p, i64p, i64p, i32p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "mr_comm_init": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),

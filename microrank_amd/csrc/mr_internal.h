@@ -428,6 +428,16 @@ struct mr_spans {
     // on this table and kept: the table is immutable.  Nothing else reads or writes it.
     mutable DBuf<unsigned long long> csum;
     mutable bool csum_ok = false;
+    // replica evidence (mr_replicas.hip): the pod-ops with rows grouped by their service-op, built by the
+    // first mr_windows_replicas call on this table and kept: rp_off[s] .. rp_off[s + 1] are service-op s's
+    // pod-ops in rp_pods (code order), rp_rank[p] the place of pod-op p inside its group (-1: no row).
+    // rp_sv_h / rp_off_h: host copies of sv(p) (-1: no row) and of rp_off, for the asked codes' slots.
+    // rp_state: 0 not built, 1 built, 2 the table is ambiguous (rp_bad: a pod-op and its two service-ops),
+    // so that later calls fail without a rebuild.  Nothing else reads or writes them.
+    mutable DBuf<int32_t> rp_off, rp_pods, rp_rank;
+    mutable std::vector<int32_t> rp_sv_h, rp_off_h;
+    mutable int rp_state = 0;
+    mutable int32_t rp_bad[3] = {0, 0, 0};
 };
 
 int mr_spans_index(mr_ctx* ctx, mr_spans* s);

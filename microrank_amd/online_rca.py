@@ -191,6 +191,47 @@ def _write_timeline(top_list, score_list, rows):
                            [float(x) for x in _latency_ms([mx[1], mx[0]])])
 
 
+def _write_replicas(top_list, score_list, rows):
+    """replicas.csv beside result.csv: for each op of result.csv, in its order, the listed replicas of its
+    service-op in answer order (rows: window_replicas' dict), one row per replica: its rows on each side of
+    the detector's partition, the mean and the largest of their values, then the op's live replicas and the
+    replicas the table knows.  ``is_result`` is 1 on the row of the ranked pod-op itself.  A mean is sum /
+    count in float64 (0.0 for no rows); means and maxima in the SLO's unit and rounding, as calls.csv's."""
+    ranked = sorted(zip(top_list, score_list), key=lambda x: x[1], reverse=True)
+    with open("replicas.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "pod", "is_result", "count_abnormal", "count_normal", "mean_abnormal", "mean_normal",
+                    "max_abnormal", "max_normal", "live", "replicas"])
+        for service, _ in ranked:
+            r = rows.get(service)
+            if r is None:
+                continue
+            for rank, e in enumerate(r["entries"], start=1):
+                mean = [np.float64(e[3 + k]) / np.float64(e[1 + k]) if e[1 + k] else np.float64(0.0) for k in (0, 1)]
+                w.writerow([service, rank, e[0], int(e[0] == service), int(e[1]), int(e[2])] +
+                           [float(x) for x in _latency_ms(mean)] + [float(x) for x in _latency_ms([e[5], e[6]])] +
+                           [int(r["live"]), int(r["all"])])
+
+
+def _replica_args(m, what="self"):
+    """(m, MR_LAT_* code) of the replicas keywords: m an integer in 1..32, what "self" or "duration";
+    ValueError otherwise -- before any device work."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 32:
+        raise ValueError(f"the replicas per op must be an integer in 1..32, not {m!r}")
+    w = _lib.LATENCY_VALUES.get(what) if isinstance(what, str) else None
+    if w is None:
+        raise ValueError(f"what must be one of {sorted(_lib.LATENCY_VALUES)}, not {what!r}")
+    return int(m), w
+
+
+def _replica_names(table, rows):
+    """windows_replicas' dict of one window with pod-op names (ops and replicas) where the table has them."""
+    names = table.podop_names
+    if names is None:
+        return rows
+    return {names[c]: dict(r, entries=[(names[e[0]],) + e[1:] for e in r["entries"]]) for c, r in rows.items()}
+
+
 def _timeline_args(buckets, what="self"):
     """(buckets, MR_LAT_* code) of the timeline keywords: buckets an integer in 1..512, what "self" or
     "duration"; ValueError otherwise -- before any device work."""
@@ -297,7 +338,7 @@ def sweep_chain(plan):
 
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
-               latency_what="self", kind_breakdown=None, call_edges=None, timeline=None):
+               latency_what="self", kind_breakdown=None, call_edges=None, timeline=None, replicas=None):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     latency (a q, scalar or sequence): ONE windows_latency call over the triggered windows' top lists;
@@ -308,8 +349,13 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     plan["calls"] = {m: windows_call_edges' dict} (calls.csv).
     timeline (an integer 1..512, the buckets): ONE windows_timeline call over the triggered windows -- the
     window's own traces (-1), then its top list; plan["timeline"] = {m: windows_timeline's dict}
-    (timeline.csv)."""
+    (timeline.csv).
+    replicas (an integer 1..32): ONE windows_replicas call over the triggered windows' top lists;
+    plan["replicas"] = {m: windows_replicas' dict} (replicas.csv)."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
+    plan.pop("replicas", None)
+    if replicas is not None:
+        replicas = _replica_args(replicas)[0]
     plan.pop("latency", None)
     plan.pop("kinds", None)
     plan.pop("calls", None)
@@ -342,6 +388,9 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     if timeline is not None:
         tl = windows_timeline(plan["ctx"], wins, [[-1] + r[0].tolist() for r in ranked], buckets=timeline)
         plan["timeline"] = dict(zip(todo, tl))
+    if replicas is not None:
+        rp = windows_replicas(plan["ctx"], wins, [r[0] for r in ranked], m=replicas)
+        plan["replicas"] = dict(zip(todo, rp))
     return dict(zip(todo, ranked))
 
 
@@ -367,14 +416,14 @@ def _sweep_plan_dev(table, dev, slo, start, end, window_normal, window_abnormal,
 
 
 def _sweep_run(plan, iters=ITERATIONS, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self",
-               kind_breakdown=None, call_edges=None, timeline=None):
+               kind_breakdown=None, call_edges=None, timeline=None, replicas=None):
     """The chain, one batched ranking of its triggered windows, then the driver's output replayed
     in window order; an empty window raises the reference's TypeError (T2) after the output of
     the windows before it."""
     events = sweep_chain(plan)
     _sweep_emit(plan, events, sweep_rank(plan, events, iters=iters, exemplars=exemplars, exemplar_kinds=exemplar_kinds,
                                          latency=latency, latency_what=latency_what, kind_breakdown=kind_breakdown,
-                                         call_edges=call_edges, timeline=timeline),
+                                         call_edges=call_edges, timeline=timeline, replicas=replicas),
                 exemplar_kinds)
 
 
@@ -422,11 +471,13 @@ def _sweep_emit(plan, events, results, exemplar_kinds=False):
             _write_calls(top_list, score_list, _call_names(plan["table"], plan["calls"][mm]))
         if "timeline" in plan:  # (timeline asked: the batch's answer, by name)
             _write_timeline(top_list, score_list, _timeline_names(plan["table"], plan["timeline"][mm]))
+        if "replicas" in plan:  # (replicas asked: the batch's answer, by name)
+            _write_replicas(top_list, score_list, _replica_names(plan["table"], plan["replicas"][mm]))
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
                               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                              call_edges=None, timeline=None):
+                              call_edges=None, timeline=None, replicas=None):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -483,7 +534,19 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     the largest self time (the SLO's unit and rounding, as calls.csv; a mean of no rows is 0.0).  From
     ONE windows_timeline call over the triggered windows on the sweep path, a call per window otherwise;
     tables whose window times vary within a trace are not covered (the call raises).  stdout and
-    result.csv do not change; without it no file is written."""
+    result.csv do not change; without it no file is written.
+
+    replicas: an integer m (1..32): every trigger also rewrites ``replicas.csv`` beside result.csv
+    (columns result, rank, pod, is_result, count_abnormal, count_normal, mean_abnormal, mean_normal,
+    max_abnormal, max_normal, live, replicas): is it the pod, or the operation?  For each op of result.csv,
+    in its order, the m pod-ops of the same service-op (the op itself among them, ``is_result`` 1) with the
+    most spans on the abnormal traces -- their spans on each side of the detector's partition with the mean
+    and the largest self time (the SLO's unit and rounding, as calls.csv; a mean of no rows is 0.0) --
+    then the replicas with a span in the window (``live``) and those the table knows (``replicas``).  From
+    ONE windows_replicas call over the triggered windows on the sweep path, a call per window otherwise.
+    stdout and result.csv do not change; without it no file is written."""
+    if replicas is not None:
+        replicas = _replica_args(replicas)[0]
     if timeline is not None:
         timeline = _timeline_args(timeline)[0]
     if call_edges is not None:
@@ -503,13 +566,13 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     plan = _sweep_plan(data, slo, start, end, window_normal, window_abnormal, ctx)
     if plan is not None:
         return _sweep_run(plan, iters, exemplars, exemplar_kinds, latency, latency_what, kind_breakdown, call_edges,
-                          timeline)
+                          timeline, replicas)
     _window_loop(data, slo, operation_list, start, end, iters, exemplars, exemplar_kinds, latency, latency_what,
-                 kind_breakdown, call_edges, timeline)
+                 kind_breakdown, call_edges, timeline, replicas)
 
 
 def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS, exemplars=None, exemplar_kinds=False,
-                 latency=None, latency_what="self", kind_breakdown=None, call_edges=None, timeline=None):
+                 latency=None, latency_what="self", kind_breakdown=None, call_edges=None, timeline=None, replicas=None):
     """online_rca.py:164-216 window by window from current_time while it is before end; returns
     where the chain goes on."""
     window_normal = pd.Timedelta(minutes=5)
@@ -550,6 +613,8 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
             if timeline is not None:
                 _write_timeline(top_list, score_list,
                                 window_timeline(data, start_time, end_time, slo, top_list, buckets=timeline))
+            if replicas is not None:
+                _write_replicas(top_list, score_list, window_replicas(data, start_time, end_time, slo, top_list, m=replicas))
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -569,15 +634,16 @@ class RCAStream:
     exemplar_kinds: its keywords (exemplars.csv rewritten at every trigger); latency, latency_what: its
     keywords (latency.csv rewritten at every trigger); kind_breakdown: its keyword (kinds.csv rewritten
     at every trigger); call_edges: its keyword (calls.csv rewritten at every trigger); timeline: its keyword
-    (timeline.csv rewritten at every trigger)."""
+    (timeline.csv rewritten at every trigger); replicas: its keyword (replicas.csv rewritten at every trigger)."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
                  exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-                 timeline=None):
+                 timeline=None, replicas=None):
         check_converge_args(0.0, iters, 1)
+        self.replicas = None if replicas is None else _replica_args(replicas)[0]
         self.timeline = None if timeline is None else _timeline_args(timeline)[0]
         self.call_edges = None if call_edges is None else _call_m(call_edges)
         self.kind_breakdown = None if kind_breakdown is None else _kind_m(kind_breakdown)
@@ -655,7 +721,7 @@ class RCAStream:
                 if final:
                     self.cur = _window_loop(data, self.slo, self.operation_list, self.cur, limit, self.iters, self.exemplars,
                                             self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
-                                            self.call_edges, self.timeline)
+                                            self.call_edges, self.timeline, self.replicas)
                 else:
                     self.cur = self._loop_complete(data, limit)
             else:
@@ -664,7 +730,8 @@ class RCAStream:
                                                      exemplar_kinds=self.exemplar_kinds, latency=self.latency,
                                                      latency_what=self.latency_what,
                                                      kind_breakdown=self.kind_breakdown,
-                                                     call_edges=self.call_edges, timeline=self.timeline),
+                                                     call_edges=self.call_edges, timeline=self.timeline,
+                                                     replicas=self.replicas),
                             self.exemplar_kinds)
                 self.cur = self.cur + pd.Timedelta(plan["next_m"] * plan["grain"], unit="ns")
         except TypeError:
@@ -683,7 +750,7 @@ class RCAStream:
         while cur < limit:
             nxt = _window_loop(data, self.slo, self.operation_list, cur, cur + pd.Timedelta(1, unit="ns"), self.iters,
                                self.exemplars, self.exemplar_kinds, self.latency, self.latency_what, self.kind_breakdown,
-                               self.call_edges, self.timeline)
+                               self.call_edges, self.timeline, self.replicas)
             cur = nxt
         return cur
 
@@ -764,7 +831,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
                exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-               timeline=None):
+               timeline=None, replicas=None):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -789,8 +856,13 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     list.  Every other key stays what it is.
 
     timeline: an integer B (1..512) adds the key ``"timeline"``: window_timeline's dict for the window's
-    own traces (key -1) and then the ops of the top list, over B buckets.  Every other key stays what it is."""
+    own traces (key -1) and then the ops of the top list, over B buckets.  Every other key stays what it is.
+
+    replicas: an integer m (1..32) adds the key ``"replicas"``: window_replicas' dict for the ops of the top
+    list, m replicas each.  Every other key stays what it is."""
     tol = _iter_args(iters, tol, check_every, info, dict)
+    if replicas is not None:
+        replicas = _replica_args(replicas)[0]
     if timeline is not None:
         timeline = _timeline_args(timeline)[0]
     if call_edges is not None:
@@ -843,6 +915,9 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     if timeline is not None:
         res["timeline"] = window_timeline(data, start_time, end_time, slo, res["top"], buckets=timeline, ctx=ctx,
                                           table=table, dev=dev)
+    if replicas is not None:
+        res["replicas"] = window_replicas(data, start_time, end_time, slo, res["top"], m=replicas, ctx=ctx, table=table,
+                                          dev=dev)
     return res
 
 
@@ -1158,6 +1233,79 @@ def window_timeline(data, start_time, end_time, slo, ops, *, buckets=30, what="s
     for b in range(0, len(asked), 64):
         rows.update(windows_timeline(ctx, [win], [asked[b:b + 64]], buckets=buckets, what=what)[0])
     return {key: _timeline_lists(rows[c]) for key, c in zip([-1] + ops, asked)}
+
+
+def windows_replicas(ctx, windows, ops, *, m=8, what="self"):
+    """Is it the pod, or the operation (mr_windows_replicas, csrc/mr_replicas.hip)?  ``windows`` as
+    rank_windows'; ``ops`` one sequence of pod-op codes per window -- the first element of rank_windows'
+    tuples.  A pod-op's replicas are the pod-ops that share its service-op on the table's rows.  Returns
+    per window {code: {"entries": [(pod code, cnt_abn, cnt_nor, sum_abn, sum_nor, max_abn, max_nor), ...],
+    "live": int, "all": int, "place": int, "own": (6 ints, the entries' order), "total": (6 ints)}}:
+    ``entries`` the first m replicas among those with a span in the window -- most abnormal spans first, then
+    fewest normal ones, then the smallest code; the asked op is a replica like any other -- with the spans
+    on each side of the window's own detector partition, the sum (int64, wrapping) and the largest of their
+    values in raw duration units (``what``: "self", duration minus the children's, or "duration"; a max of no
+    span is 0); ``live`` the replicas with a span in the window, ``all`` those the table knows, ``place`` the
+    asked op's 0-based place among ALL live replicas (-1: it has no span in the window; it can be >= m),
+    ``own`` its own numbers, listed or not, and ``total`` the numbers over all live replicas: the service-op's
+    own.  An empty window (rank_windows' status MR_ERR_VALUE) answers empty entries, place -1 and zeros.
+    ValueError for m outside 1..32, an unknown what, more than 64 ops in a window or len(ops) !=
+    len(windows); time windows on tables without trace-level times, self time on a trace shard and tables
+    where a pod-op has rows of two service-ops are not covered (RuntimeError from the library)."""
+    m, wcode = _replica_args(m, what)
+    n = len(windows)
+    asked, k, cod, n_ops = _asked_args(ops, n)
+    if n == 0:
+        return []
+    keep, spans, t0, t1, a3, ok = _window_args(windows)
+    pod = np.zeros((n, k, m), np.int32)
+    cnt, tot, mx = (np.zeros((n, k, m, 2), np.int64) for _ in range(3))
+    cn, live, every, place = (np.zeros((n, k), np.int32) for _ in range(4))
+    own, total = np.zeros((n, k, 2, 3), np.int64), np.zeros((n, k, 2, 3), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_replicas(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                              ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, m, wcode, ptr(pod, C.c_int32),
+                                              ptr(cnt, C.c_int64), ptr(tot, C.c_int64), ptr(mx, C.c_int64),
+                                              ptr(cn, C.c_int32), ptr(live, C.c_int32), ptr(every, C.c_int32),
+                                              ptr(place, C.c_int32), ptr(own, C.c_int64), ptr(total, C.c_int64),
+                                              ptr(status, C.c_int32)), "mr_windows_replicas")
+    # (plain lists: a call answers thousands of entries, and indexing numpy scalars would cost more than the call)
+    # and an entry's tuples come from one zip over the seven planes, abnormal before normal)
+    planes = [a[..., side].tolist() for a in (cnt, tot, mx) for side in (1, 0)]
+    pl, nl, ll, al, el = pod.tolist(), cn.tolist(), live.tolist(), every.tolist(), place.tolist()
+
+    def six(v):   # [.., side, {cnt, sum, max}] -> (cnt_abn, cnt_nor, sum_abn, sum_nor, max_abn, max_nor)
+        return v[:, :, ::-1, :].transpose(0, 1, 3, 2).reshape(n, k, 6).tolist()
+
+    ol, tl = six(own), six(total)
+
+    def one(i, j):
+        return {"entries": list(zip(pl[i][j][:nl[i][j]], *[p[i][j] for p in planes])), "live": ll[i][j], "all": al[i][j],
+                "place": el[i][j], "own": tuple(ol[i][j]), "total": tuple(tl[i][j])}
+
+    return [{c: one(i, j) for j, c in enumerate(asked[i])} for i in range(n)]
+
+
+def window_replicas(data, start_time, end_time, slo, ops, *, m=8, what="self", ctx=None, table=None, dev=None):
+    """windows_replicas for one window by names: {pod-op: {"entries", "live", "all", "place", "own", "total"}}
+    for the pod-ops of ``ops`` (names, or codes), replicas by name where the table has names.  An op that is
+    no pod-op of the table raises ValueError; ops past the call's 64 slots go in further calls."""
+    m, _ = _replica_args(m, what)
+    ops = list(ops)
+    ctx = ctx or _lib.default_context()
+    if table is None or dev is None:
+        table, dev = span_table(data, ctx)
+    codes = _op_codes(table, ops)
+    if not ops:
+        return {}
+    a3, ok = slo_arrays(table, slo)
+    win = (dev, to_ns(start_time), to_ns(end_time), a3, ok)
+    rows = {}
+    for b in range(0, len(codes), 64):
+        rows.update(windows_replicas(ctx, [win], [codes[b:b + 64]], m=m, what=what)[0])
+    names = table.podop_names
+    pn = (lambda c: names[c]) if names is not None else (lambda c: c)
+    return {key: dict(rows[c], entries=[(pn(e[0]),) + e[1:] for e in rows[c]["entries"]]) for key, c in zip(ops, codes)}
 
 
 def _exemplar_rows(n, k, m, codes, n_out, ex_t, ex_s, ex_c, ex_m=None):
