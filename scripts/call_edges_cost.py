@@ -16,7 +16,8 @@ waits for):
       dictionary stays in cache and is not counted).
 
   (e) one windows_latency call (q = 0.5 and 0.99, self time) and one windows_timeline call (30 buckets, self
-      time) over the N windows: each top list.
+      time) over the N windows: each top list;
+  (f) one windows_replicas call over the N windows: each top list, m = 8, self time.
 
 The GPU work runs in one child process under `timeout`; the parent never opens the GPU.
 
@@ -28,6 +29,10 @@ MR_LIB_PATH, alternating parent, this tree, parent, this tree, each under `timeo
 ends the run.  Per timed entry the mean of this tree's two medians against the larger of the parent's two
 times 1.03 (DESIGN §4's box-to-box spread); the parent's own two medians say how far one build moves between
 processes.  The result goes to profiles/evidence_front.json.
+
+--parent-tree DIR (a checkout of the commit before) asks the same of a change to the Python side: the four
+children alternate DIR's package and this tree's, all four over this tree's library, and the bar applies to
+the medians by HIP events and to those by the host's clock.  The result goes to profiles/evidence_python.json.
 """
 import argparse
 import json
@@ -43,7 +48,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
 from converge_cost import Events  # noqa: E402  (scripts/ is sys.path[0])
 
 CALLS, WARMUP, M = 7, 2, 8
-TIMED = ("ranking_step", "kind_breakdown", "call_edges", "latency", "timeline")
+TIMED = ("ranking_step", "kind_breakdown", "call_edges", "latency", "timeline", "replicas")
 SPREAD = 1.03
 
 
@@ -55,10 +60,13 @@ def summary(v):
 def child(a):
     import ctypes as C
 
+    if a.tree:   # (the package and bench.py of another checkout, ahead of this one's)
+        sys.path.insert(0, os.path.abspath(a.tree))
     import bench
     from microrank_amd import _lib
     from microrank_amd.online_rca import (rank_windows, windows_call_edges, windows_kind_breakdown, windows_latency,
-                                          windows_timeline)
+                                          windows_replicas, windows_timeline)
+    assert os.path.dirname(os.path.abspath(_lib.__file__)) == os.path.join(os.path.abspath(a.tree or REPO), "microrank_amd")
     from microrank_amd.preprocess_data import DeviceSpans
 
     tabs = bench.c2_window_stream(a.windows, a.ops, a.traces, 0)   # (the generators fork before the GPU is touched)
@@ -93,6 +101,7 @@ def child(a):
     res["call_edges"] = timed(lambda: keep.__setitem__("c", windows_call_edges(ctx, wins, tops, m=M)))
     res["latency"] = timed(lambda: windows_latency(ctx, wins, tops, q=(0.5, 0.99), what="self"))
     res["timeline"] = timed(lambda: windows_timeline(ctx, wins, tops, buckets=30, what="self"))
+    res["replicas"] = timed(lambda: windows_replicas(ctx, wins, tops, m=M, what="self"))
     listed = [sum(len(side[0]) for v in w.values() for side in v) for w in keep["c"]]
     res["listed_edges_per_window"] = [min(listed), max(listed)]
     res["calls_per_window_abn_nor"] = [[sum(v[1][2][k] for v in w.values()) for k in (0, 1)] for w in keep["c"][:4]]
@@ -108,7 +117,7 @@ def child(a):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def run_child(a, role, libpath):
+def run_child(a, role, libpath, tree=None):
     """One child process under `timeout`: its RESULT line, or None when the step failed."""
     env = dict(os.environ)
     env.pop("MR_LIB_PATH", None)
@@ -116,6 +125,7 @@ def run_child(a, role, libpath):
         env["MR_LIB_PATH"] = os.path.abspath(libpath)
     cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", role,
            "--windows", str(a.windows), "--ops", str(a.ops), "--traces", str(a.traces)]
+    cmd += ["--tree", tree] if tree else []
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
     if p.returncode != 0 or not line:
@@ -124,12 +134,12 @@ def run_child(a, role, libpath):
     return json.loads(line[-1][len("RESULT "):])
 
 
-def compare(steps):
-    """Per timed entry: the four medians by HIP events and whether this tree keeps the parent's time."""
+def compare(steps, clock="event_ms_median"):
+    """Per timed entry: the four medians by ``clock`` and whether this tree keeps the parent's time."""
     out = {}
     for what in TIMED:
-        old = [s[what]["event_ms_median"] for s in steps if s["lib"] == "parent"]
-        new = [s[what]["event_ms_median"] for s in steps if s["lib"] == "new"]
+        old = [s[what][clock] for s in steps if s["lib"] == "parent"]
+        new = [s[what][clock] for s in steps if s["lib"] == "new"]
         bar = max(old) * SPREAD
         out[what] = {"parent_ms": old, "new_ms": new, "new_mean_ms": statistics.mean(new), "bar_ms": bar,
                      "within_bar": statistics.mean(new) <= bar, "parent_spread": max(old) / min(old),
@@ -143,17 +153,26 @@ def main():
     ap.add_argument("--ops", type=int, default=1000)
     ap.add_argument("--traces", type=int, default=200_000)
     ap.add_argument("--parent-lib", default=None, help="another build of libmicrorank_hip.so: compare against it")
-    ap.add_argument("--out", default=None, help="default: profiles/call_edges.json, with --parent-lib profiles/evidence_front.json")
+    ap.add_argument("--parent-tree", default=None,
+                    help="a checkout of the commit before: compare its Python package against this one's")
+    ap.add_argument("--tree", default=None, help="(internal) the checkout a child takes the package from")
+    ap.add_argument("--out", default=None, help="default: profiles/call_edges.json, evidence_front.json with --parent-lib, "
+                                                "evidence_python.json with --parent-tree")
     ap.add_argument("--step-timeout", type=int, default=840)
     ap.add_argument("--child", default=None, help="(internal) run the GPU step; the value names the library")
     a = ap.parse_args()
     if a.child:
         return child(a)
-    out = a.out or os.path.join(REPO, "profiles", "evidence_front.json" if a.parent_lib else "call_edges.json")
-    if a.parent_lib:
+    if a.parent_lib and a.parent_tree:
+        ap.error("--parent-lib and --parent-tree are two questions: ask one")
+    out = a.out or os.path.join(REPO, "profiles", "evidence_python.json" if a.parent_tree else
+                                "evidence_front.json" if a.parent_lib else "call_edges.json")
+    if a.parent_lib or a.parent_tree:
         steps = []
+        own = os.path.join(REPO, "microrank_amd", "libmicrorank_hip.so") if a.parent_tree else None   # (one library for all)
         for role in ("parent", "new", "parent", "new"):
-            r = run_child(a, role, a.parent_lib if role == "parent" else None)
+            old = role == "parent"
+            r = run_child(a, role, own or (a.parent_lib if old else None), a.parent_tree if old else None)
             if r is None:   # nothing more on the GPU after a step that failed
                 sys.exit(1)
             print(json.dumps({k: r[k]["event_ms_median"] for k in TIMED} | {"lib": role}), flush=True)
@@ -161,6 +180,10 @@ def main():
         res = {"windows": a.windows, "ops": a.ops, "traces": a.traces, "calls": CALLS, "warmup": WARMUP, "m": M,
                "spread": SPREAD, "entries": compare(steps), "steps": steps}
         shown = res["entries"]
+        if a.parent_tree:   # (host code changed: the host's clock is held to the bar too)
+            res["entries_host_clock"] = compare(steps, "host_ms_median")
+            res["all_within_bar"] = all(e["within_bar"] for k in ("entries", "entries_host_clock") for e in res[k].values())
+            shown = {k: res[k] for k in ("entries", "entries_host_clock", "all_within_bar")}
     else:
         res = shown = run_child(a, "new", None)
         if res is None:
