@@ -11,8 +11,10 @@ constexpr int RC = 8;                 // chunks of RT keys per block (tile = 204
 constexpr int RTILE = RT * RC;
 constexpr int NW = RT / WAVE;
 
-__global__ void __launch_bounds__(RT) k_radix_hist(const uint64_t* keys, int64_t n, int shift, int64_t nb,
-                                                   int64_t* hist) {
+// dmask: the digit's bits that lie below `bits` (255, but for a last pass of bits % 8 bits: the
+// key bits above `bits` do not order -- the callers size `bits` to their keys and have none there)
+__global__ void __launch_bounds__(RT) k_radix_hist(const uint64_t* keys, int64_t n, int shift, uint32_t dmask,
+                                                   int64_t nb, int64_t* hist) {
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -20,7 +22,7 @@ __global__ void __launch_bounds__(RT) k_radix_hist(const uint64_t* keys, int64_t
 #pragma unroll
     for (int c = 0; c < RC; ++c) {
         int64_t i = base + (int64_t)c * RT + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & dmask], 1u);
     }
     __syncthreads();
     hist[(int64_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major
@@ -38,8 +40,8 @@ __device__ __forceinline__ uint64_t peers_of(uint32_t digit) {
 
 template <bool HASV>
 __global__ void __launch_bounds__(RT) k_radix_scatter(const uint64_t* keys, const uint32_t* vals, uint64_t* okeys,
-                                                      uint32_t* ovals, int64_t n, int shift, int64_t nb,
-                                                      const int64_t* offs) {
+                                                      uint32_t* ovals, int64_t n, int shift, uint32_t dmask,
+                                                      int64_t nb, const int64_t* offs) {
     __shared__ int64_t run[256];
     __shared__ uint32_t wcnt[NW][256];
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
@@ -52,7 +54,7 @@ __global__ void __launch_bounds__(RT) k_radix_scatter(const uint64_t* keys, cons
         const int64_t i = base + (int64_t)c * RT + threadIdx.x;
         const bool valid = i < n;
         uint64_t k = valid ? keys[i] : 0ull;
-        uint32_t dg = valid ? (uint32_t)((k >> shift) & 255u) : 256u;   // 256: sentinel, never written
+        uint32_t dg = valid ? (uint32_t)((k >> shift) & dmask) : 256u;   // 256: sentinel, never written
         uint64_t act = __ballot(valid);
         uint64_t pm = peers_of(dg & 255u) & act;
         if (!valid) pm = 0;
@@ -154,14 +156,16 @@ int mr_radix_sort(mr_ctx* ctx, uint64_t* keys, uint32_t* vals, int64_t n, int bi
     const int passes = (bits + 7) / 8;
     for (int p = 0; p < passes; ++p) {
         const int shift = 8 * p;
-        hipLaunchKernelGGL(k_radix_hist, dim3((unsigned)nb), dim3(RT), 0, ctx->stream, ka, n, shift, nb, ws.hist.p);
+        const uint32_t dmask = bits - shift >= 8 ? 255u : (1u << (bits - shift)) - 1u;
+        hipLaunchKernelGGL(k_radix_hist, dim3((unsigned)nb), dim3(RT), 0, ctx->stream, ka, n, shift, dmask, nb,
+                           ws.hist.p);
         MR_TRY(mr_exclusive_scan(ctx, ws.hist.p, ws.hist.p, 256 * nb, ws.tmp.p));
         if (vals)
             hipLaunchKernelGGL(k_radix_scatter<true>, dim3((unsigned)nb), dim3(RT), 0, ctx->stream, ka, va, kb, vb, n,
-                               shift, nb, ws.hist.p);
+                               shift, dmask, nb, ws.hist.p);
         else
             hipLaunchKernelGGL(k_radix_scatter<false>, dim3((unsigned)nb), dim3(RT), 0, ctx->stream, ka, va, kb, vb, n,
-                               shift, nb, ws.hist.p);
+                               shift, dmask, nb, ws.hist.p);
         std::swap(ka, kb);
         std::swap(va, vb);
     }
