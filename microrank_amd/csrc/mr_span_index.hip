@@ -58,8 +58,10 @@ __global__ void k_ix_cnt(const int64_t* r_start, int64_t R, int64_t n, int32_t* 
     if (r < R) r_cnt[r] = (int32_t)((r + 1 < R ? r_start[r + 1] : n) - r_start[r]);
 }
 // per-trace scalars: rows, max duration, min/max of trace-level start and end
-// (rows of a trace are mostly adjacent: lanes of one trace are combined over the wave first and
-// the run's last lane alone updates the trace; runs of one trace split over waves merge exactly)
+// (rows of a trace are mostly adjacent but need not be: each contiguous run of one trace's rows is
+// combined over the wave first -- a lane takes a partner only from its own run, so the row count
+// is a sum over the run and nothing else -- and the run's last lane alone updates the trace; a
+// trace's runs, in one wave or in several, merge exactly in the atomics)
 __global__ void k_ix_trace_stats(const int32_t* trace, const int64_t* dur, const int64_t* ts, const int64_t* te, int64_t S,
                                  int32_t* tlen, long long* tmaxd, long long* tsmin, long long* tsmax, long long* temin,
                                  long long* temax) {
@@ -71,13 +73,17 @@ __global__ void k_ix_trace_stats(const int32_t* trace, const int64_t* dur, const
     long long s0 = in && ts ? (long long)ts[i] : LLONG_MAX, s1 = in && ts ? (long long)ts[i] : LLONG_MIN;
     long long e0 = in && ts ? (long long)te[i] : LLONG_MAX, e1 = in && ts ? (long long)te[i] : LLONG_MIN;
     const int lane = threadIdx.x & 63;
+    // run heads: lane 0 and every lane whose trace differs from the lane below; a lane's run starts
+    // at the highest head at or below it
+    const int32_t tp = __shfl_up(t, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || tp != t);
+    const int start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {   // inclusive segmented scan over runs of equal t
-        const int32_t to = __shfl_up(t, off, 64);
+    for (int off = 1; off < 64; off <<= 1) {   // inclusive segmented scan over the contiguous runs
         const int32_t no = __shfl_up(n, off, 64);
         const long long mo = __shfl_up(md, off, 64), a0 = __shfl_up(s0, off, 64), a1 = __shfl_up(s1, off, 64),
                         b0 = __shfl_up(e0, off, 64), b1 = __shfl_up(e1, off, 64);
-        if (lane >= off && to == t) {
+        if (lane - off >= start) {
             n += no;
             md = max(md, mo);
             s0 = min(s0, a0);
