@@ -411,6 +411,20 @@ int mr_windows_batch_ex(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* s
                         int32_t top_max, int precision, int32_t* out_podop, double* out_score, int32_t* n_out,
                         int64_t* edges_traversed, int32_t* n_abnormal, int32_t* n_normal, int32_t* status,
                         int iters, double tol, int check_every, int32_t* iters_done, double* resid);
+/* A test and diagnostic hook, not part of the ranking interface: how the windows of tables with a
+ * layout order were built, counted over the process since the library was loaded (process-wide
+ * counters; MR_WIN_PHASES prints the same two numbers).  The window build
+ * has two forms with the same result: the direct form adds every entry of the window's traces
+ * into its two graphs; the complement form takes the larger graph (the detector's normal traces)
+ * as the table's totals minus everything else and walks only the other traces' entries.  A table
+ * carries what the complement form needs when its index could build it; a window takes that form
+ * when the table's time summary says it leaves out at most a quarter of the table's traces.
+ * MR_LO_COMPLEMENT (read per call): 0 always direct, 1 complement wherever the table allows.
+ *   n_complement  windows launched in the complement form
+ *   n_rebuilt     of those, windows built again in the direct form because the table's first-row
+ *                 candidates of some op all lay outside the window's normal traces
+ * Either pointer may be NULL. */
+int mr_lo_complement_counts(int64_t* n_complement, int64_t* n_rebuilt);
 /* mr_windows_batch_ex that also says WHICH TRACES: for every op of a window's top list the ex_m
  * traces to open, read from the state the window's ranking leaves on the device before its graphs
  * are released.  Every argument of mr_windows_batch_ex in its order, then:

@@ -442,6 +442,11 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
     // zeroed buffer
     bool batched = false, lo = false;
     DBuf<uint32_t> zw;
+    std::vector<const mr_spans*> sps((size_t)n);   // (the layout-order build's arguments: a window may be rebuilt)
+    std::vector<mr_graph*> g0((size_t)n), g1((size_t)n);
+    std::vector<IxBuild*> b0((size_t)n), b1((size_t)n);
+    std::vector<int64_t*> outs((size_t)n);
+    std::vector<uint32_t*> zs((size_t)n);
     {
         bool ok = getenv("MR_NO_LO_WIN") == nullptr;   // (A/B and tests, read per call)
         int64_t nzw = 0;
@@ -451,11 +456,6 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
         }
         if (ok) {
             MR_TRY(zw.zero(ctx, (size_t)nzw));
-            std::vector<const mr_spans*> sps((size_t)n);
-            std::vector<mr_graph*> g0((size_t)n), g1((size_t)n);
-            std::vector<IxBuild*> b0((size_t)n), b1((size_t)n);
-            std::vector<int64_t*> outs((size_t)n);
-            std::vector<uint32_t*> zs((size_t)n);
             int64_t zo = 0;
             for (int k = 0; k < n; ++k) {
                 sps[(size_t)k] = in[k].s;
@@ -531,6 +531,22 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
         unsigned char* hp = nullptr;
         MR_TRY(mr_read_bytes(ctx, wb.p, h.size() * sizeof(int64_t), &hp));
         memcpy(h.data(), hp, h.size() * sizeof(int64_t));
+        // a complement-form window whose graph 1 holds an op but none of its first-row candidates
+        // (word 7 of graph 1's sizes): its words zeroed and the window built again in the direct form
+        bool again = false;
+        for (int k = 0; k < n && lo; ++k) {
+            if (!h[(size_t)k * WW + CW + 15]) continue;
+            again = true;
+            mr_lo_cmp_note_rebuild();
+            MR_TRY_HIP(ctx, hipMemsetAsync(wb.p + (size_t)k * WW, 0, WW * sizeof(int64_t), st));
+            MR_TRY_HIP(ctx, hipMemsetAsync(zs[(size_t)k], 0, (size_t)mr_lo_zero_words(in[k].s) * sizeof(uint32_t), st));
+            MR_TRY(mr_lo_launch_batch(ctx, 1, &sps[(size_t)k], &g0[(size_t)k], &g1[(size_t)k], &b0[(size_t)k],
+                                      &b1[(size_t)k], &outs[(size_t)k], &dis[(size_t)k], &zs[(size_t)k], true));
+        }
+        if (again) {
+            MR_TRY(mr_read_bytes(ctx, wb.p, h.size() * sizeof(int64_t), &hp));
+            memcpy(h.data(), hp, h.size() * sizeof(int64_t));
+        }
     }
     WinPhase ph2(2);
     // MR_WIN_SETUP_SPLIT: traces of a window from which it sets up here (default 65536): small
@@ -1283,7 +1299,9 @@ static int windows_batch_run(mr_ctx* ctx, int32_t n_windows, const mr_spans* con
         }
         fprintf(stderr, "[mr_windows_batch] %d windows, %.3f ms:", n_windows, (win_now() - t_call) * 1e-6);
         for (int i = 0; i < 10; ++i) fprintf(stderr, " %s %.3f ms;", WIN_PHASE_NAME[i], g_phases->ns[i] * 1e-6);
-        fprintf(stderr, "\n");
+        int64_t ncmp = 0, nreb = 0;   // (since the library was loaded)
+        mr_lo_cmp_counts(&ncmp, &nreb);
+        fprintf(stderr, " complement-form builds %lld, rebuilt directly %lld\n", (long long)ncmp, (long long)nreb);
         g_phases = nullptr;
     }
     return MR_OK;

@@ -13,6 +13,7 @@
 //      op-major side is derived by mr_graph_prepare as tiles); call edges sorted by
 //      (child, parent) give P_ss by child.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -2170,6 +2171,8 @@ struct IxWinLoB {
     uint32_t* kcnt[2];               // kind class histograms (zeroed)
     int64_t* tot[2];                 // [T, nnz] (zeroed)
     uint32_t* rows;                  // partial rows [block][graph][cnt NP | cov NP | INT_MAX - first NP | edges nek]
+    int32_t cmp, pad_;               // complement form: graph 1's histogram holds the traces in NEITHER graph
+    uint32_t* nrow;                  // ... added into this zeroed row by the blocks that have any (no partial row)
 };
 // the build's first LDS region: both graphs' histograms, and before them (aliased) the detector's
 // products of a round -- at least 2048 of them
@@ -2199,6 +2202,8 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
     __shared__ uint32_t pst[LO_BT_MAX + 1], est[LO_BT_MAX + 1];   // the traces' first entries (relative)
     __shared__ int8_t ss[LO_BT_MAX];
     __shared__ unsigned long long bc[5][LB_T / WAVE];
+    __shared__ uint16_t kl[LO_BT_MAX];   // complement form: the range's traces outside graph 1
+    __shared__ uint32_t nkl, nnei;
     const int k = ixb_pick(a.b0, a.n);
     const IxWinLoB& w = a.w[k];
     const int32_t blk = (int32_t)blockIdx.x - a.b0[k];
@@ -2217,6 +2222,7 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
     if (tid == 0) {
         pst[nt] = np;
         est[nt] = nq;
+        nkl = nnei = 0u;
     }
     // this thread's traces: slot s holds trace s * LB_T + tid of the range (64 consecutive per wave)
     constexpr int NS = LO_BT_MAX / LB_T;
@@ -2311,6 +2317,15 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
             if (c0) atomicAdd(&w.kcnt[0][kid], c0);
             if (c1) atomicAdd(&w.kcnt[1][kid], c1);
         }
+        if (w.cmp) {   // the traces whose entries this form walks: one list slot each, a wave's together
+            const bool keep = valid && s_ != 1;
+            const unsigned long long K = __ballot(keep);
+            uint32_t base = 0u;
+            if (lane == 0 && K) base = atomicAdd(&nkl, (uint32_t)__popcll(K));
+            if (lane == 0 && (K & ~B0)) atomicAdd(&nnei, (uint32_t)__popcll(K & ~B0));
+            base = (uint32_t)__shfl((int)base, 0, WAVE);
+            if (keep) kl[base + (uint32_t)__popcll(K & ((1ull << lane) - 1ull))] = (uint16_t)t;
+        }
     }
     __syncthreads();
     // the range's pod-op and join entries, each to its trace's graph.  A range of short traces (the
@@ -2318,8 +2333,59 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
     // walks its own entries, all loads out at once, no lookups, each trace's entries rotated by its
     // index (a run of identical traces would otherwise add into the same word in the same round).
     // Else every wave over the range's entries, a lane per entry, the entry's trace looked up.
+    // The complement form (w.cmp) walks the entries of the listed traces only -- graph 0's into
+    // histogram 0, those of the traces in neither graph into histogram 1 (no first rows: the
+    // reduce subtracts both from the table's totals) -- and loads nothing of a graph-1 trace:
+    // sixteen lanes per listed trace, two traces' first loads in flight per group.
+    if (w.cmp) {
+        constexpr int GL = 16, NG = LB_T / GL;
+        const uint32_t nk = nkl, gl = (uint32_t)tid & (GL - 1);
+        for (uint32_t x0 = (uint32_t)tid / GL; x0 < nk; x0 += 2 * NG) {
+            uint32_t a0[2], n[2], b0e[2], m[2], pc[2], ev[2];
+            int32_t fr[2];
+            bool g0[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const uint32_t x = x0 + (uint32_t)(u * NG);
+                const int32_t t = kl[x < nk ? x : x0];
+                g0[u] = ss[t] == 0;
+                a0[u] = pst[t];
+                n[u] = x < nk ? pst[t + 1] - a0[u] : 0u;
+                b0e[u] = est[t];
+                m[u] = x < nk ? est[t + 1] - b0e[u] : 0u;
+                pc[u] = ev[u] = 0u;
+                fr[u] = 0;
+                if (gl < n[u]) {
+                    const int64_t e = P0 + (int64_t)(a0[u] + gl);
+                    pc[u] = (uint32_t)w.lo16[e] | ((uint32_t)w.lo_cnt[e] << 16);
+                    if (g0[u]) fr[u] = w.lo_first[e];
+                }
+                if (gl < m[u]) ev[u] = w.le[Q0 + (int64_t)(b0e[u] + gl)];
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                unsigned char* G = lraw + (g0[u] ? (size_t)0 : gbytes);
+                int32_t* Gf = (int32_t*)(G + (size_t)NP * 8);
+                uint32_t* Ge = (uint32_t*)(G + (size_t)NP * 12);
+                for (uint32_t j = gl; j < n[u]; j += GL) {
+                    if (j >= GL) {
+                        const int64_t e = P0 + (int64_t)(a0[u] + j);
+                        pc[u] = (uint32_t)w.lo16[e] | ((uint32_t)w.lo_cnt[e] << 16);
+                        if (g0[u]) fr[u] = w.lo_first[e];
+                    }
+                    const uint32_t c = pc[u] & 0xffffu;
+                    atomicAdd((unsigned long long*)G + c, (unsigned long long)(pc[u] >> 16) | (1ull << 32));
+                    if (g0[u]) atomicMax(Gf + c, 0x7fffffff - fr[u]);
+                }
+                for (uint32_t j = gl; j < m[u]; j += GL) {
+                    if (j >= GL) ev[u] = w.le[Q0 + (int64_t)(b0e[u] + j)];
+                    atomicAdd(Ge + (ev[u] & 0xffffu), ev[u] >> 16);
+                }
+            }
+        }
+    }
     constexpr int LB_LANE = 8;
-    const bool lanewise = nt > 0 && pst[nt] - pst[nt - 1] <= (uint32_t)LB_LANE;
+    const bool lanewise = !w.cmp && nt > 0 && pst[nt] - pst[nt - 1] <= (uint32_t)LB_LANE;
     if (lanewise) {
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
@@ -2362,7 +2428,7 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
     const uint32_t n0 = nt ? pst[1 < nt ? 1 : nt] - pst[0] : 0u;
     const uint32_t npo = n0 > 0 && np == (uint32_t)nt * n0 ? n0 : 0u;   // (uniform: every trace n0 entries)
     constexpr int NW = LB_T / WAVE;
-    const uint32_t nmax = lanewise ? 0u : max(np, nq);
+    const uint32_t nmax = lanewise || w.cmp ? 0u : max(np, nq);
     for (uint32_t b0 = (uint32_t)wv * (LB_R * WAVE); b0 < nmax; b0 += NW * LB_R * WAVE) {
         uint32_t pc[LB_R], ev[LB_R];
         int32_t fr[LB_R];
@@ -2418,7 +2484,19 @@ __global__ void __launch_bounds__(LB_T, 6) k_lo_build_b(IxBatch<IxWinLoB> a) {
     // the block's histograms as its partial row (plain stores; k_lo_reduce_b combines the rows)
     const size_t rw = 3 * (size_t)NP + (size_t)nek;
     uint32_t* R = w.rows + (size_t)blk * 2 * rw;
-    for (int g = 0; g < 2; ++g) {
+    if (w.cmp && nnei != 0u) {   // (few blocks of a window that takes this form: the traces it leaves out)
+        const unsigned char* G = lraw + gbytes;
+        for (int32_t c = tid; c < NP; c += LB_T) {
+            const unsigned long long v = ((const unsigned long long*)G)[c];
+            if ((uint32_t)v) atomicAdd(&w.nrow[c], (uint32_t)v);
+            if ((uint32_t)(v >> 32)) atomicAdd(&w.nrow[NP + c], (uint32_t)(v >> 32));
+        }
+        for (int32_t x = tid; x < nek; x += LB_T) {
+            const uint32_t v = ((const uint32_t*)(G + (size_t)NP * 12))[x];
+            if (v) atomicAdd(&w.nrow[3 * NP + x], v);
+        }
+    }
+    for (int g = 0; g < (w.cmp ? 1 : 2); ++g) {
         const unsigned char* G = lraw + (size_t)g * gbytes;
         uint32_t* Rg = R + (size_t)g * rw;
         for (int32_t c = tid; c < NP; c += LB_T) {
@@ -2505,36 +2583,78 @@ struct IxLoRed {
     int32_t nblk, NP, nek, pad_;
     int32_t *ocnt[2], *ofinv[2], *ocov[2];
     uint32_t* gc[2];
+    // complement form (tot non-null; a thread per column of BOTH graphs): graph 1's additive words
+    // are the table's totals (laid out as a row) minus graph 0's column minus the word of the
+    // traces in neither graph (nrow: the build's blocks added theirs).  Graph 1's first row
+    // of an op it holds: the first of the op's candidates (mr_spans.lo_cand: sorted by first row,
+    // a complete prefix of the op's entries) whose trace the window put into graph 1; none: *flag.
+    const uint32_t* tot;
+    const uint32_t* nrow;
+    const int8_t* side;
+    const uint64_t* ckey;
+    const uint32_t* cix;
+    const int64_t* coff;
+    int64_t* flag;
+    int32_t crb, pad2_;
 };
-__global__ void __launch_bounds__(256) k_lo_reduce_b(IxBatch<IxLoRed> a) {
-    const int k = ixb_pick(a.b0, a.n);
-    const IxLoRed& w = a.w[k];
-    const int64_t rw = 3 * (int64_t)w.NP + w.nek;
-    const int64_t col = (int64_t)((int32_t)blockIdx.x - a.b0[k]) * 256 + threadIdx.x;
-    if (col >= 2 * rw) return;
-    const int g = (int)(col / rw);
-    const int64_t c = col - (int64_t)g * rw;
-    const bool mx = c >= 2 * (int64_t)w.NP && c < 3 * (int64_t)w.NP;
-    const uint32_t* p = w.rows + col;
-    const size_t stride = 2 * (size_t)rw;
+__device__ __forceinline__ uint32_t lo_col(const uint32_t* p, size_t stride, int32_t nblk, bool mx) {
     uint32_t acc = 0;
     int32_t b = 0;
-    for (; b + 8 <= w.nblk; b += 8) {
+    for (; b + 8 <= nblk; b += 8) {
         uint32_t v[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = p[(size_t)(b + q) * stride];
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc = mx ? max(acc, v[q]) : acc + v[q];
     }
-    for (; b < w.nblk; ++b) {
+    for (; b < nblk; ++b) {
         const uint32_t v = p[(size_t)b * stride];
         acc = mx ? max(acc, v) : acc + v;
     }
+    return acc;
+}
+__device__ __forceinline__ void lo_put(const IxLoRed& w, int g, int64_t c, uint32_t v) {
     const int32_t NP = w.NP;
-    if (c < NP) w.ocnt[g][c] = (int32_t)acc;
-    else if (c < 2 * (int64_t)NP) w.ocov[g][c - NP] = (int32_t)acc;
-    else if (c < 3 * (int64_t)NP) w.ofinv[g][c - 2 * NP] = (int32_t)acc;
-    else w.gc[g][c - 3 * NP] = acc;
+    if (c < NP) w.ocnt[g][c] = (int32_t)v;
+    else if (c < 2 * (int64_t)NP) w.ocov[g][c - NP] = (int32_t)v;
+    else if (c < 3 * (int64_t)NP) w.ofinv[g][c - 2 * NP] = (int32_t)v;
+    else w.gc[g][c - 3 * NP] = v;
+}
+__global__ void __launch_bounds__(256) k_lo_reduce_b(IxBatch<IxLoRed> a) {
+    const int k = ixb_pick(a.b0, a.n);
+    const IxLoRed& w = a.w[k];
+    const int64_t rw = 3 * (int64_t)w.NP + w.nek;
+    const int64_t col = (int64_t)((int32_t)blockIdx.x - a.b0[k]) * 256 + threadIdx.x;
+    const size_t stride = 2 * (size_t)rw;
+    if (w.tot == nullptr) {   // direct form: a thread per (graph, column)
+        if (col >= 2 * rw) return;
+        const int g = (int)(col / rw);
+        const int64_t c = col - (int64_t)g * rw;
+        const bool mx = c >= 2 * (int64_t)w.NP && c < 3 * (int64_t)w.NP;
+        lo_put(w, g, c, lo_col(w.rows + col, stride, w.nblk, mx));
+        return;
+    }
+    if (col >= rw) return;
+    const bool mx = col >= 2 * (int64_t)w.NP && col < 3 * (int64_t)w.NP;
+    const uint32_t a0 = lo_col(w.rows + col, stride, w.nblk, mx);
+    lo_put(w, 0, col, a0);
+    if (mx) return;
+    const uint32_t v1 = w.tot[col] - a0 - w.nrow[col];
+    lo_put(w, 1, col, v1);
+    if (col < w.NP && v1 > 0u) {
+        // (one thread, a chain of dependent reads: at most LO_CMP_SCAN candidates -- where 93 % of the
+        // traces are normal the first or second is one; past the cap the window is rebuilt like one whose
+        // candidates ran out)
+        int32_t fi = 0;
+        const int64_t j1 = min(w.coff[col + 1], w.coff[col] + (int64_t)LO_CMP_SCAN);
+        for (int64_t j = w.coff[col]; j < j1; ++j)
+            if (w.side[w.cix[j]] == 1) {
+                fi = 0x7fffffff - (int32_t)(uint32_t)(w.ckey[j] & ((1ull << w.crb) - 1ull));
+                break;
+            }
+        w.ofinv[1][col] = fi;
+        if (fi == 0) *w.flag = 1;
+    }
 }
 
 // Per window (n <= IXW): k_lo_build_b, the rare joins across traces, the node order / P_ss / op
@@ -2542,15 +2662,44 @@ __global__ void __launch_bounds__(256) k_lo_reduce_b(IxBatch<IxLoRed> a) {
 // T, nnz; words 5 / 6: the build's totals).  zw[k]: the window's zeroed words, lo_zero_words(sp)
 // of them.  MR_ERR_STATE: a window outside the limits (the caller takes mr_ix_launch2_batch).
 int64_t mr_lo_zero_words(const mr_spans* sp) {
-    return 2 * ((int64_t)std::max(sp->lo_nk, 1) + 3 * (int64_t)sp->n_podops + std::max<int64_t>(sp->n_edge_keys, 1));
+    // per graph the kind histogram and the graph's words; then the complement form's row of the traces in
+    // neither graph (a partial row's layout)
+    return 2 * ((int64_t)std::max(sp->lo_nk, 1) + 3 * (int64_t)sp->n_podops + std::max<int64_t>(sp->n_edge_keys, 1)) +
+           3 * (int64_t)sp->n_podops + std::max<int64_t>(sp->n_edge_keys, 1);
+}
+// an upper bound of the table's traces that the window [t0, t1] leaves out of both graphs, from the
+// time summary: the traces no window selects, every start bucket that reaches below t0 and every
+// end bucket that reaches above t1
+static int64_t lo_cmp_out_bound(const mr_spans* sp, int64_t t0, int64_t t1) {
+    int64_t out = sp->lo_ninact;
+    for (int b = 0; b < 64; ++b) {
+        const __int128 lo = (__int128)sp->lo_tmin + (__int128)b * sp->lo_tbw;
+        const __int128 hi = std::min<__int128>(lo + sp->lo_tbw - 1, sp->lo_tmax);   // (no end lies past lo_tmax)
+        if (lo < (__int128)t0) out += sp->lo_hts[b];
+        if (hi > (__int128)t1) out += sp->lo_hte[b];
+    }
+    return out;
+}
+static std::atomic<int64_t> g_lo_cmp_windows{0}, g_lo_cmp_rebuilt{0};
+void mr_lo_cmp_counts(int64_t* n_cmp, int64_t* n_rebuilt) {
+    if (n_cmp) *n_cmp = g_lo_cmp_windows.load();
+    if (n_rebuilt) *n_rebuilt = g_lo_cmp_rebuilt.load();
+}
+void mr_lo_cmp_note_rebuild() { ++g_lo_cmp_rebuilt; }
+extern "C" int mr_lo_complement_counts(int64_t* n_complement, int64_t* n_rebuilt) {
+    mr_lo_cmp_counts(n_complement, n_rebuilt);
+    return MR_OK;
 }
 int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph* const* g0s, mr_graph* const* g1s,
                        IxBuild* const* b0s, IxBuild* const* b1s, int64_t* const* d_outs, const DetIn* dets,
-                       uint32_t* const* zw) {
+                       uint32_t* const* zw, bool force_direct) {
     if (n < 1 || n > IXW || getenv("MR_NO_IX2") != nullptr) return MR_ERR_STATE;
     for (int k = 0; k < n; ++k)
         if (!sps[k]->lo_ok || !mr_lo_fits(sps[k])) return MR_ERR_STATE;
     hipStream_t st = ctx->stream;
+    const char* ce = getenv("MR_LO_COMPLEMENT");   // (read per call: 0 direct, 1 complement, else by the summary)
+    const int cmode = force_direct || (ce && ce[0] == '0') ? 0 : ce && ce[0] == '1' ? 1 : -1;
+    std::vector<char> cmps((size_t)n);
     IxBatch<IxWinLoB> ab{};
     IxBatch<IxLoRed> ar{};
     IxBatch<IxWinLoPos> ap{};
@@ -2618,7 +2767,10 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
         ar.w[k].NP = NP;
         ar.w[k].nek = (int32_t)nek;
         ar.b0[k] = br;
-        br += (int32_t)cdiv(2 * rw, 256);
+        const bool cmp = sp->lo_cmp_ok && cmode != 0 &&
+                         (cmode == 1 || 4 * lo_cmp_out_bound(sp, dets[k].t0, dets[k].t1) <= (int64_t)NT);
+        cmps[(size_t)k] = cmp;
+        br += (int32_t)cdiv(cmp ? rw : 2 * rw, 256);
         const int32_t npb = (int32_t)std::max<int64_t>(cdiv((int64_t)NT, LP_TILE), 1);
         woff[(size_t)k] = words;
         words += 2 * (int64_t)npb;
@@ -2630,6 +2782,16 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
         ab.b0[k] = bb;
         bb += nt;
         const DetIn& d = dets[k];
+        L.cmp = cmp ? 1 : 0;
+        L.pad_ = 0;
+        IxLoRed& R = ar.w[k];
+        R.tot = cmp ? sp->lo_tot.p : nullptr;
+        R.ckey = sp->lo_cand_key.p;
+        R.cix = sp->lo_cand_ix.p;
+        R.coff = sp->lo_cand_off.p;
+        R.crb = sp->lo_cand_rb;
+        R.pad2_ = 0;
+        R.flag = d_outs[k] + 15;
         L.bstart = sp->lo_bstart.p;
         L.lo_tr = sp->lo_tr.p;
         L.lo_len = sp->lo_len.p;
@@ -2681,6 +2843,14 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
         ar.w[k].rows = rows.p + roff[(size_t)k];
         ab.w[k].side = side.p + soff[(size_t)k];
         ap.w[k].side = side.p + soff[(size_t)k];
+        ar.w[k].side = side.p + soff[(size_t)k];
+        {   // (the row of the traces in neither graph: the last of the window's zeroed words)
+            const mr_spans* sp = sps[k];
+            uint32_t* nr = zw[k] + 2 * ((int64_t)std::max(sp->lo_nk, 1) + 3 * (int64_t)sp->n_podops +
+                                        std::max<int64_t>(sp->n_edge_keys, 1));
+            ab.w[k].nrow = nr;
+            ar.w[k].nrow = nr;
+        }
         ap.w[k].st = dst + woff[(size_t)k];
     }
     hipLaunchKernelGGL(k_lo_build_b, dim3(bb), dim3(LB_T), lds, st, ab);
@@ -2689,6 +2859,7 @@ int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph*
     if (bc) hipLaunchKernelGGL(k_ix_cross2_b, dim3(bc), dim3(256), 0, st, ac);
     hipLaunchKernelGGL(k_nodes_small2_b, dim3(2 * n), dim3(NS_T), 0, st, an);
     MR_TRY_HIP(ctx, hipGetLastError());
+    for (int k = 0; k < n; ++k) g_lo_cmp_windows += cmps[(size_t)k] ? 1 : 0;   // (launched)
     return MR_OK;
 }
 

@@ -411,6 +411,32 @@ struct mr_spans {
     int32_t lo_nblk = 0;
     DBuf<int64_t> lsv_off, le_off;       // [NT+1] service-op entries / join entries of each trace
     DBuf<uint32_t> lsv, le;              // svcop | count << 16 (code order); dense edge id | count << 16
+    // The complement form of the window build (lo_cmp_ok; built with the layout, best effort: a
+    // failure leaves the table on the direct form).  Span counts, coverage and edge multiplicities
+    // are sums over traces and the table is immutable, so a window's graph 1 (its normal traces, the
+    // bulk of a window) is the table's totals minus graph 0 minus the traces in neither graph, and
+    // the build walks only the entries of the traces that are NOT normal.
+    //   lo_tot   the totals over every layout entry, laid out as a partial row of the build:
+    //            [span count NP | coverage NP | (unused) NP | edge multiplicity n_edge_keys]
+    //   lo_cand  first rows are minima and do not subtract: per op the entries whose first row is
+    //            below a per-op threshold -- at least LO_CMP_K of them, or all the op has -- sorted
+    //            by (op, first row): op c's are lo_cand_off[c] .. lo_cand_off[c + 1], each a key
+    //            (op << lo_cand_rb | first row) and its trace's layout index.  They are a complete
+    //            prefix of the op's entries by first row, so the first of them whose trace a window
+    //            put into graph 1 carries the op's first row there.  A window whose graph 1 has the
+    //            op but none of its candidates is rebuilt directly.
+    //   lo_hts / lo_hte  host: 64-bucket counts of the traces' starts / ends over [lo_tmin, lo_tmax]
+    //            (bucket width lo_tbw) and lo_ninact traces that no window selects: a bound on the
+    //            traces a window leaves out, for the choice of the form (mr_lo_launch_batch)
+    bool lo_cmp_ok = false;
+    DBuf<uint32_t> lo_tot;               // [3 n_podops + n_edge_keys]
+    DBuf<uint64_t> lo_cand_key;          // [lo_ncand]
+    DBuf<uint32_t> lo_cand_ix;           // [lo_ncand]
+    DBuf<int64_t> lo_cand_off;           // [n_podops + 1]
+    int64_t lo_ncand = 0;
+    int lo_cand_rb = 0;                  // bits of a first row in a key
+    int64_t lo_tmin = 0, lo_tmax = 0, lo_tbw = 1, lo_ninact = 0;
+    int64_t lo_hts[64] = {}, lo_hte[64] = {};
     // tables ingested from strings (mr_spans_ingest): the first row of each trace / pod-op /
     // service-op code, in code order (the host builds the name lists from them)
     DBuf<int32_t> dict_rows[3];
@@ -611,10 +637,20 @@ bool mr_lo_fits(const mr_spans* sp);
 // most LO_BE pod-op entries: the layout's long traces spread over many blocks
 constexpr int32_t LO_BT_MAX = 1024;
 constexpr int64_t LO_BE = 12288;
+constexpr int32_t LO_CMP_K = 16;   // first-row candidates per op at least (mr_spans.lo_cand)
+constexpr int32_t LO_CMP_SCAN = 256;   // ... and at most this many of an op read per window (k_lo_reduce_b)
 int64_t mr_lo_zero_words(const mr_spans* sp);
+// The form per window: the complement form (graph 1 = the table's totals minus graph 0 minus the
+// rest; mr_spans.lo_cmp_ok) when the table's time summary bounds the traces outside [t0, t1] at a
+// quarter of the table; MR_LO_COMPLEMENT (read per call) 0: always direct, 1: complement wherever
+// lo_cmp_ok.  Both forms give the same words.  force_direct: every window direct (the rebuild of a
+// window whose first-row candidates ran out: word 7 of its graph 1's d_outs is then nonzero).
 int mr_lo_launch_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, mr_graph* const* g0s, mr_graph* const* g1s,
                        IxBuild* const* b0s, IxBuild* const* b1s, int64_t* const* d_outs, const DetIn* dets,
-                       uint32_t* const* zw);
+                       uint32_t* const* zw, bool force_direct = false);
+// windows built in the complement form / rebuilt directly after it, since the library was loaded
+void mr_lo_cmp_counts(int64_t* n_cmp, int64_t* n_rebuilt);
+void mr_lo_cmp_note_rebuild();
 // their prepare and PageRank set-up (tiles, ids, kinds, preference, iteration state: pre_ok) in
 // four launches; gs[i] built from sps[i / 2] with builds bs[i]
 int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const* sps, IxBuild* const* bs,

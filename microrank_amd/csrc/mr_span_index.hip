@@ -318,6 +318,200 @@ __global__ void k_lo_classes(const int32_t* head, const int64_t* hpos, const int
     if (!eq) atomicOr(bad, 1);
 }
 
+// ---------------------------------------------------------------- complement form (mr_spans.lo_cmp_ok)
+// The table's totals, first-row candidates and time summary (mr_internal.h), from the layout copies.
+constexpr int LC_T = 256;
+// the totals: an LDS histogram per block over the pod-op and join entries (grid-stride, coalesced),
+// flushed with one global add per nonzero word; tot as a partial row of the build
+__global__ void __launch_bounds__(LC_T) k_lo_cmp_tot(const uint16_t* lo16, const uint16_t* lo_cnt, int64_t n_po,
+                                                     const uint32_t* le, int64_t n_ed, int32_t NP, int32_t nek,
+                                                     uint32_t* tot) {
+    extern __shared__ uint32_t lch[];   // span count NP | coverage NP | edge multiplicity nek
+    const int32_t nw = 2 * NP + nek;
+    for (int32_t i = threadIdx.x; i < nw; i += LC_T) lch[i] = 0u;
+    __syncthreads();
+    const int64_t e0 = (int64_t)blockIdx.x * LC_T + threadIdx.x, stride = (int64_t)gridDim.x * LC_T;
+    for (int64_t e = e0; e < n_po; e += stride) {
+        const uint32_t c = lo16[e];
+        atomicAdd(&lch[c], (uint32_t)lo_cnt[e]);
+        atomicAdd(&lch[NP + c], 1u);
+    }
+    for (int64_t e = e0; e < n_ed; e += stride) {
+        const uint32_t v = le[e];
+        atomicAdd(&lch[2 * NP + (v & 0xffffu)], v >> 16);
+    }
+    __syncthreads();
+    for (int32_t i = threadIdx.x; i < nw; i += LC_T)
+        if (lch[i]) atomicAdd(&tot[i < 2 * NP ? i : i + NP], lch[i]);
+}
+// an op's first candidate threshold from the count n of its entries: where first rows spread evenly
+// over the table's S rows, 4 LO_CMP_K entries lie below it (an op of no more entries: all of them)
+__device__ __forceinline__ int64_t lo_cmp_r1(int64_t S, uint32_t n) {
+    return n <= 4u * (uint32_t)LO_CMP_K ? S : S * (4 * LO_CMP_K) / (int64_t)n + 1;
+}
+// per op: its entries below that threshold and below eight times it (below: [2 NP], zeroed)
+__global__ void __launch_bounds__(LC_T) k_lo_cmp_below(const uint16_t* lo16, const int32_t* lo_first, int64_t n_po,
+                                                       int32_t NP, int64_t S, const uint32_t* tot, uint32_t* below) {
+    extern __shared__ uint32_t lch[];
+    for (int32_t i = threadIdx.x; i < 2 * NP; i += LC_T) lch[i] = 0u;
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * LC_T;
+    for (int64_t e = (int64_t)blockIdx.x * LC_T + threadIdx.x; e < n_po; e += stride) {
+        const uint32_t c = lo16[e];
+        const int64_t f = lo_first[e], r1 = lo_cmp_r1(S, tot[NP + c]);
+        if (f < r1) atomicAdd(&lch[c], 1u);
+        if (f < 8 * r1) atomicAdd(&lch[NP + c], 1u);
+    }
+    __syncthreads();
+    for (int32_t i = threadIdx.x; i < 2 * NP; i += LC_T)
+        if (lch[i]) atomicAdd(&below[i], lch[i]);
+}
+// per op: the lowest of the thresholds (r1, 8 r1, every row) below which it has LO_CMP_K entries or
+// all of its entries
+// (ccnt: the entries it then has below it; *cmax: the most any op has)
+__global__ void k_lo_cmp_thr(int32_t NP, int64_t S, const uint32_t* tot, const uint32_t* below, int32_t* thr,
+                             int32_t* ccnt, unsigned long long* cmax) {
+    const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= NP) return;
+    const uint32_t n = tot[NP + c], b1 = below[c], b8 = below[NP + c];
+    const int64_t r1 = lo_cmp_r1(S, n);
+    const bool t1 = b1 >= (uint32_t)LO_CMP_K || b1 == n, t8 = b8 >= (uint32_t)LO_CMP_K || b8 == n;
+    const int64_t r = t1 ? r1 : t8 ? 8 * r1 : (int64_t)INT32_MAX;
+    thr[c] = (int32_t)min(r, (int64_t)INT32_MAX);
+    ccnt[c] = (int32_t)(t1 ? b1 : t8 ? b8 : n);
+    atomicMax(cmax, (unsigned long long)(t1 ? b1 : t8 ? b8 : n));
+}
+// the candidates: every entry below its op's threshold as a key (op << rb | first row) with its
+// trace's layout index, into the op's segment (coff, from k_lo_cmp_thr's counts) at a slot from the
+// op's cursor (cur, zeroed) -- any order inside the segment, sorted after.  Entry-parallel and
+// coalesced, LC_E entries per lane; only a hit looks up its trace: a fixed-step search over lo_off
+// (P2: the power of two >= NT), a lane's searches side by side so that their loads overlap.
+constexpr int LC_E = 8;
+__global__ void __launch_bounds__(LC_T) k_lo_cmp_cand(const int64_t* lo_off, const uint16_t* lo16, const int32_t* lo_first,
+                                                      int64_t n_po, int32_t NT, int32_t P2, const int32_t* thr, int rb,
+                                                      const int64_t* coff, uint32_t* cur, uint64_t* c_key, uint32_t* c_ix) {
+    const int tid = threadIdx.x;
+    for (int64_t b0 = (int64_t)blockIdx.x * (LC_T * LC_E); b0 < n_po; b0 += (int64_t)gridDim.x * (LC_T * LC_E)) {
+        int32_t f[LC_E], lo[LC_E];
+        uint32_t c[LC_E];
+        bool hit[LC_E];
+#pragma unroll
+        for (int u = 0; u < LC_E; ++u) {
+            const int64_t e = b0 + u * LC_T + tid;
+            c[u] = e < n_po ? (uint32_t)lo16[e] : 0u;
+            f[u] = e < n_po ? lo_first[e] : INT32_MAX;
+            lo[u] = 0;
+        }
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < LC_E; ++u) {
+            hit[u] = f[u] != INT32_MAX && f[u] < thr[c[u]];
+            any = any || hit[u];
+        }
+        if (!any) continue;
+        for (int32_t step = P2 >> 1; step >= 1; step >>= 1) {   // the last index whose lo_off is <= e
+#pragma unroll
+            for (int u = 0; u < LC_E; ++u)
+                if (hit[u]) {
+                    const int32_t mid = lo[u] + step;
+                    if (mid < NT && lo_off[mid] <= b0 + u * LC_T + tid) lo[u] = mid;
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < LC_E; ++u)
+            if (hit[u]) {
+                const int64_t o = coff[c[u]] + (int64_t)atomicAdd(&cur[c[u]], 1u);
+                if (o < coff[c[u] + 1]) {
+                    c_key[o] = ((uint64_t)c[u] << rb) | (uint64_t)(uint32_t)f[u];
+                    c_ix[o] = (uint32_t)lo[u];
+                }
+            }
+    }
+}
+// each op's segment sorted by key (its first rows ascending; keys are distinct: a row belongs to one
+// trace): a block per op, a bitonic network in LDS over at most LCS_MAX candidates (the host takes the
+// radix sort for a table with a longer segment)
+constexpr int LCS_MAX = 2048;
+__global__ void __launch_bounds__(LC_T) k_lo_cmp_sort(const int64_t* coff, uint64_t* c_key, uint32_t* c_ix) {
+    __shared__ uint64_t sk[LCS_MAX];
+    __shared__ uint32_t sv[LCS_MAX];
+    const int64_t a = coff[blockIdx.x];
+    const int32_t n = (int32_t)(coff[blockIdx.x + 1] - a);
+    if (n <= 1 || n > LCS_MAX) return;
+    int32_t m = 1;
+    while (m < n) m <<= 1;
+    for (int32_t i = threadIdx.x; i < m; i += LC_T) {
+        sk[i] = i < n ? c_key[a + i] : ~0ull;
+        sv[i] = i < n ? c_ix[a + i] : 0u;
+    }
+    __syncthreads();
+    for (int32_t k = 2; k <= m; k <<= 1)
+        for (int32_t j = k >> 1; j > 0; j >>= 1) {
+            for (int32_t i = threadIdx.x; i < m; i += LC_T) {
+                const int32_t l = i ^ j;
+                if (l > i) {
+                    const uint64_t x = sk[i], y = sk[l];
+                    if (((i & k) == 0) == (x > y)) {   // ascending in the lower half of each k-run
+                        const uint32_t vx = sv[i], vy = sv[l];
+                        sk[i] = y;
+                        sk[l] = x;
+                        sv[i] = vy;
+                        sv[l] = vx;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    for (int32_t i = threadIdx.x; i < n; i += LC_T) {
+        c_key[a + i] = sk[i];
+        c_ix[a + i] = sv[i];
+    }
+}
+// the time summary.  mm: the least start and greatest end of the traces a window can select, as
+// order-preserving unsigned words (x ^ 2^63), preset to ~0 and 0
+__device__ __forceinline__ bool lo_cmp_active(int32_t len, long long mx) { return len > 0 && mx > 0; }
+__global__ void k_lo_cmp_trange(const long long* lo_ts, const long long* lo_te, const int32_t* lo_len,
+                                const long long* lo_mx, int32_t NT, unsigned long long* mm) {
+    unsigned long long lo = ~0ull, hi = 0ull;   // (grid-stride: a pair of atomics per wave of a small grid)
+    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < NT; i += gridDim.x * blockDim.x)
+        if (lo_cmp_active(lo_len[i], lo_mx[i])) {
+            lo = min(lo, (unsigned long long)lo_ts[i] ^ (1ull << 63));
+            hi = max(hi, (unsigned long long)lo_te[i] ^ (1ull << 63));
+        }
+    for (int m = WAVE / 2; m >= 1; m >>= 1) {
+        lo = min(lo, (unsigned long long)__shfl_xor((long long)lo, m, WAVE));
+        hi = max(hi, (unsigned long long)__shfl_xor((long long)hi, m, WAVE));
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        if (lo != ~0ull) atomicMin(&mm[0], lo);
+        if (hi != 0ull) atomicMax(&mm[1], hi);
+    }
+}
+// hist: starts [64] | ends [64] | the traces no window selects [1] (zeroed), buckets of
+// (max - min) / 64 + 1 from the least start
+__global__ void __launch_bounds__(LC_T) k_lo_cmp_thist(const long long* lo_ts, const long long* lo_te,
+                                                       const int32_t* lo_len, const long long* lo_mx, int32_t NT,
+                                                       const unsigned long long* mm, unsigned long long* hist) {
+    __shared__ uint32_t h[129];
+    if (threadIdx.x < 129) h[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned long long lo = mm[0], hi = mm[1];
+    const unsigned long long w = hi >= lo ? (hi - lo) / 64 + 1 : 1ull;
+    const int32_t i = blockIdx.x * LC_T + threadIdx.x;
+    if (i < NT) {
+        if (lo_cmp_active(lo_len[i], lo_mx[i])) {
+            const unsigned long long a = (unsigned long long)lo_ts[i] ^ (1ull << 63);
+            const unsigned long long b = (unsigned long long)lo_te[i] ^ (1ull << 63);
+            atomicAdd(&h[a <= lo ? 0 : (int)min((a - lo) / w, 63ull)], 1u);
+            atomicAdd(&h[64 + (b <= lo ? 0 : (int)min((b - lo) / w, 63ull))], 1u);
+        } else {
+            atomicAdd(&h[128], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 129 && h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
 // ---------------------------------------------------------------- window detector (uniform times)
 // (the per-block body: mr_detect_dev.h)
 __global__ void __launch_bounds__(DB) k_ix_detect(int32_t NT, DetIn d) {
@@ -561,7 +755,89 @@ static int lo_index_try(mr_ctx* ctx, mr_spans* s) {
     }
     return MR_OK;   // (four colliding seeds: the general window path)
 }
+static void lo_cmp_release(mr_spans* s) {
+    s->lo_cmp_ok = false;
+    s->lo_ncand = 0;
+    s->lo_tot.reset();
+    s->lo_cand_key.reset();
+    s->lo_cand_ix.reset();
+    s->lo_cand_off.reset();
+}
+// What the complement form of the window build needs from a table with a layout (mr_internal.h):
+// the totals, the first-row candidates and the host's time summary, from the layout copies.
+static int lo_cmp_index_try(mr_ctx* ctx, mr_spans* s) {
+    hipStream_t st = ctx->stream;
+    const int32_t NT = s->n_traces, NP = s->n_podops, nek = (int32_t)s->n_edge_keys;
+    s->lo_cmp_ok = false;
+    const size_t rw = 3 * (size_t)NP + (size_t)nek;
+    MR_TRY(s->lo_tot.zero(ctx, std::max<size_t>(rw, 1)));
+    if (getenv("MR_LO_CMP_TEST_FAIL"))   // (tests, read per table: an allocation failing half-way)
+        return mr_fail(ctx, MR_ERR_HIP, "lo_cmp_index: forced failure (MR_LO_CMP_TEST_FAIL)");
+    DBuf<uint32_t> below;
+    DBuf<int32_t> thr, ccnt;
+    DBuf<int64_t> tmp;
+    DBuf<unsigned long long> tsum;   // least start, greatest end, k_lo_cmp_thist's 129 counters, k_lo_cmp_cand's cursor
+    MR_TRY(below.zero(ctx, 3 * (size_t)std::max(NP, 1)));   // (the last third: k_lo_cmp_cand's cursors)
+    MR_TRY(thr.alloc(ctx, (size_t)std::max(NP, 1)));
+    MR_TRY(ccnt.alloc(ctx, (size_t)std::max(NP, 1)));
+    MR_TRY(s->lo_cand_off.alloc(ctx, (size_t)NP + 1));
+    const int rb = std::max(1, bits_for((uint64_t)std::max<int64_t>(s->S - 1, 0)));
+    MR_TRY(tmp.alloc(ctx, (size_t)scan_tmp_elems(NP)));
+    MR_TRY(tsum.zero(ctx, 132));
+    MR_TRY_HIP(ctx, hipMemsetAsync(tsum.p, 0xff, 8, st));
+    const int64_t ne = std::max<int64_t>(std::max(s->n_po, s->n_ed), 1);
+    const int eb = (int)std::min<int64_t>(cdiv(ne, (int64_t)LC_T * 16), 256);
+    hipLaunchKernelGGL(k_lo_cmp_tot, dim3(eb), dim3(LC_T), (size_t)(2 * NP + nek) * 4, st, s->lo16.p, s->lo_cnt.p, s->n_po,
+                       s->le.p, s->n_ed, NP, nek, s->lo_tot.p);
+    hipLaunchKernelGGL(k_lo_cmp_below, dim3(eb), dim3(LC_T), (size_t)(2 * NP) * 4, st, s->lo16.p, s->lo_first.p, s->n_po,
+                       NP, s->S, s->lo_tot.p, below.p);
+    hipLaunchKernelGGL(k_lo_cmp_thr, dim3(cdiv(std::max(NP, 1), XB)), dim3(XB), 0, st, NP, s->S, s->lo_tot.p, below.p,
+                       thr.p, ccnt.p, tsum.p + 131);
+    MR_TRY(mr_exclusive_scan_i32(ctx, ccnt.p, s->lo_cand_off.p, NP, tmp.p));
+    hipLaunchKernelGGL(k_lo_cmp_trange, dim3(std::min(cdiv(NT, LC_T), 64)), dim3(LC_T), 0, st, s->lo_ts.p, s->lo_te.p, s->lo_len.p,
+                       s->lo_mx.p, NT, tsum.p);
+    hipLaunchKernelGGL(k_lo_cmp_thist, dim3(cdiv(NT, LC_T)), dim3(LC_T), 0, st, s->lo_ts.p, s->lo_te.p, s->lo_len.p,
+                       s->lo_mx.p, NT, tsum.p, tsum.p + 2);
+    MR_TRY_HIP(ctx, hipGetLastError());
+    int64_t nc = 0;
+    unsigned long long ht[132];
+    MR_TRY_HIP(ctx, hipMemcpyAsync(&nc, s->lo_cand_off.p + NP, sizeof nc, hipMemcpyDeviceToHost, st));
+    MR_TRY(tsum.download(ctx, ht, 132));
+    MR_TRY_HIP(ctx, hipStreamSynchronize(st));
+    MR_TRY(s->lo_cand_key.alloc(ctx, (size_t)std::max<int64_t>(nc, 1)));
+    MR_TRY(s->lo_cand_ix.alloc(ctx, (size_t)std::max<int64_t>(nc, 1)));
+    int32_t p2 = 1;
+    while (p2 < NT) p2 <<= 1;
+    hipLaunchKernelGGL(k_lo_cmp_cand, dim3((int)std::min<int64_t>(cdiv(std::max<int64_t>(s->n_po, 1), (int64_t)LC_T * LC_E), 1024)),
+                       dim3(LC_T), 0, st, s->lo_off.p, s->lo16.p, s->lo_first.p, s->n_po, NT, p2, thr.p, rb,
+                       s->lo_cand_off.p, below.p + 2 * (size_t)std::max(NP, 1), s->lo_cand_key.p, s->lo_cand_ix.p);
+    {   // by (op, first row): an op's candidates are contiguous already (lo_cand_off); earliest first
+        SortScratch ws;
+        if ((int64_t)ht[131] <= LCS_MAX)
+            hipLaunchKernelGGL(k_lo_cmp_sort, dim3(std::max(NP, 1)), dim3(LC_T), 0, st, s->lo_cand_off.p, s->lo_cand_key.p,
+                               s->lo_cand_ix.p);
+        else if (nc > 1)   // (an op with a long segment: one sort of the whole list)
+            MR_TRY(mr_radix_sort(ctx, s->lo_cand_key.p, s->lo_cand_ix.p, nc,
+                                 rb + std::max(1, bits_for((uint64_t)std::max(NP - 1, 0))), ws));
+        MR_TRY_HIP(ctx, hipGetLastError());
+        MR_TRY_HIP(ctx, hipStreamSynchronize(st));   // (the scratch, thr and the cursors leave scope)
+    }
+    s->lo_ncand = nc;
+    s->lo_cand_rb = rb;
+    const bool any = ht[0] != ~0ull;   // (a trace that a window can select)
+    s->lo_tmin = any ? (int64_t)(ht[0] ^ (1ull << 63)) : 0;
+    s->lo_tmax = any ? (int64_t)(ht[1] ^ (1ull << 63)) : 0;
+    s->lo_tbw = any && ht[1] >= ht[0] ? (int64_t)((ht[1] - ht[0]) / 64 + 1) : 1;
+    for (int b = 0; b < 64; ++b) {
+        s->lo_hts[b] = (int64_t)ht[2 + b];
+        s->lo_hte[b] = (int64_t)ht[2 + 64 + b];
+    }
+    s->lo_ninact = (int64_t)ht[2 + 128];
+    s->lo_cmp_ok = true;
+    return MR_OK;
+}
 static void lo_release(mr_spans* s) {
+    lo_cmp_release(s);
     s->lo_ok = false;
     s->lo_nk = 0;
     s->lo_nblk = 0;
@@ -593,6 +869,13 @@ static int lo_index(mr_ctx* ctx, mr_spans* s) {
         ctx->err.clear();
     }
     if (rc != MR_OK || !s->lo_ok) lo_release(s);
+    // the complement form's data, best effort too: without it the table builds its windows directly
+    if (s->lo_ok && lo_cmp_index_try(ctx, s) != MR_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+        ctx->err.clear();
+        lo_cmp_release(s);
+    }
     return MR_OK;
 }
 
