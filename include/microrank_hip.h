@@ -707,6 +707,36 @@ int mr_windows_timeline(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* s
                         int64_t* tl_out /*[n_windows * K * 2 * 2]: window, slot, side, {before, after}*/,
                         int32_t* status /*[n_windows]*/);
 
+/* mr_windows_timeline with latency quantiles per bucket and side: lay a percentile SLO over the timeline, and
+ * tell "p50 moved: everything got slower" from "only p99 moved: a few requests hang".
+ * The arguments are mr_windows_timeline's, then q[n_q] (n_q in 1..16, every q in [0, 1]) and method (MR_Q_LINEAR
+ * / MR_Q_LOWER / MR_Q_HIGHER), as mr_windows_latency's.  tl_cnt, tl_sum, tl_max, tl_out and status are, word
+ * for word, what mr_windows_timeline writes for the same arguments.
+ *   tl_q[(((i * K + j) * B + b) * 2 + side) * n_q + k]  the q[k]-quantile of the values counted in
+ *       tl_cnt[((i * K + j) * B + b) * 2 + side], by numpy 2.x's np.quantile(values, q, method=...) on the int64
+ *       values -- for a pod-op the op's selected rows whose trace starts in bucket b, valued by `what`; for -1
+ *       the window's traces, each valued tend - tstart.  float64 in raw duration units, bit for bit
+ *       mr_slo_quantiles' arithmetic; 0.0 where the count is 0.  The two outside buckets get no quantiles.
+ * A code asked twice is answered each time; entries j >= n_ops[i] and an empty window answer zeros.
+ * Per chunk of windows: the counters as in mr_windows_timeline, then one selection of packed keys, class <<
+ * db | (value - vmin), class = ((window in chunk * slots + slot) * B + bucket) * 2 + side, db the bits of the
+ * chunk's (vmax - vmin); ONE sort, one bounds pass and one pick for the chunk -- never a launch, a sort or a host
+ * synchronisation per window, asked op or bucket.  Everything is integer until the pick, so tl_q is the same
+ * bits under any cut into blocks, any chunking, any place of a window in the call and any neighbours.
+ * MR_ERR_ARG: mr_windows_timeline's, and: n_q outside 1..16, a q outside [0, 1] (NaN too), an unknown method; a
+ * chunk whose class bits plus db exceed 64 ("value range too wide to sort", naming the range; which chunks
+ * fit depends on the cut).
+ * MR_ERR_STATE: mr_windows_timeline's list, order and messages.
+ * An argument error leaves the context usable. */
+int mr_windows_timeline_q(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                          const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                          const int32_t* podops /*[n_windows * K], -1 = the window's traces*/, const int32_t* n_ops,
+                          int32_t K, int what /*MR_LAT_DURATION | MR_LAT_SELF*/, const int64_t* b0, const int64_t* bw,
+                          int32_t B /*buckets, 1..512*/, const double* q /*[n_q]*/, int32_t n_q /*1..16*/,
+                          int method /*MR_Q_*/, int64_t* tl_cnt, int64_t* tl_sum, int64_t* tl_max, int64_t* tl_out,
+                          double* tl_q /*[n_windows * K * B * 2 * n_q]: window, slot, bucket, side, q*/,
+                          int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ replica evidence
  * Is it this POD, or is it the OPERATION?  The ranking names pod-ops (podName_op); the detector and the SLO
  * speak in service-ops (serviceName_op).  For each asked pod-op this entry answers with the pod-ops that

@@ -148,6 +148,10 @@ SIGNATURES = {
     "mr_windows_timeline": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, i64p, i64p, C.c_int32, i64p,
                                       i64p, i64p, i64p, i32p]),
+    # ... with q, n_q and method ahead of the outputs, and tl_q (float64 quantiles per bucket and side) behind tl_out
+    "mr_windows_timeline_q": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int, i64p, i64p, C.c_int32, f64p,
+                                        C.c_int32, C.c_int, i64p, i64p, i64p, i64p, f64p, i32p]),
     # replica evidence: many windows' replicas (the pod-ops of the same service-op) per asked pod-op, both sides
     "mr_windows_replicas": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, C.c_int, i32p, i64p, i64p,

@@ -470,6 +470,9 @@ int mr_spans_index(mr_ctx* ctx, mr_spans* s);
 // mr_latency.hip: s->csum computed on first use (stream-ordered) and kept with the table; mr_timeline.hip's
 // MR_LAT_SELF reads the same buffer
 int lat_csum_ensure(mr_ctx* ctx, const mr_spans* s);
+// mr_latency.hip: n_q in 1..LAT_MAX_Q, a known what and method, every q in [0, 1] (MR_ERR_ARG naming `who`)
+constexpr int LAT_MAX_Q = 16;
+int lat_args(mr_ctx* ctx, const char* who, int what, const double* q, int32_t n_q, int method);
 
 // Handles given out across the ABI (graphs, span tables) are registered with their context:
 // mr_ctx_destroy frees the ones still live, and freeing a handle that is not registered (its

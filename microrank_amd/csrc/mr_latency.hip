@@ -26,7 +26,6 @@ namespace {
 constexpr int LT = 256;            // threads per block
 constexpr int LAT_MAXB = 1024;     // k_lat_select blocks per window (grid-stride)
 constexpr int LAT_MAX_OPS = 64;    // asked ops per window (mr_graph_exemplars' op limit)
-constexpr int LAT_MAX_Q = 16;
 constexpr int LAT_MAX_Y = 32768;   // windows per k_lat_select launch (gridDim.y)
 
 struct LatWin {
@@ -213,9 +212,7 @@ int lat_csum_ensure(mr_ctx* ctx, const mr_spans* s) {
     return MR_OK;
 }
 
-namespace {
-
-// the arguments both entries share
+// the arguments both entries share (mr_internal.h: mr_windows_timeline_q checks its own the same way)
 int lat_args(mr_ctx* ctx, const char* who, int what, const double* q, int32_t n_q, int method) {
     if (n_q < 1 || n_q > LAT_MAX_Q) return mr_fail(ctx, MR_ERR_ARG, "%s: n_q = %d is not in 1..%d", who, n_q, LAT_MAX_Q);
     if (what != MR_LAT_DURATION && what != MR_LAT_SELF) return mr_fail(ctx, MR_ERR_ARG, "%s: unknown what %d", who, what);
@@ -226,6 +223,8 @@ int lat_args(mr_ctx* ctx, const char* who, int what, const double* q, int32_t n_
             return mr_fail(ctx, MR_ERR_ARG, "%s: q[%d] = %g is not in [0, 1]", who, j, q[j]);
     return MR_OK;
 }
+
+namespace {
 
 // out [nw * K * 2 * n_q] and count [nw * K * 2] (host), zeroed by the caller
 int lat_run(mr_ctx* ctx, const char* who, int64_t nw, const LatReq* rq, int32_t K, int what, const double* q, int32_t n_q,

@@ -6,6 +6,8 @@ the mapper from a batch answer to rows by name and the writer of its CSV file.  
 call order and ``evidence_request`` checks a caller's keywords into one request; the drivers in
 ``online_rca`` loop over that request and never name a kind.  A new kind is one record in ``KINDS``, its
 keyword in ``evidence_request`` and in the four public signatures of ``online_rca``, and a docstring line.
+An option of a kind (the timeline's ``timeline_q`` / ``timeline_what``) is a keyword of ``evidence_request`` that
+ends up in that kind's parameters; ``Kind.batch_for`` / ``window_for`` pick the form that takes them.
 """
 from __future__ import annotations
 
@@ -51,6 +53,27 @@ def _timeline_args(buckets, what="self"):
     """(buckets, MR_LAT_* code) of the timeline keywords: buckets an integer in 1..512, what "self" or
     "duration"; ValueError otherwise -- before any device work."""
     return _int_in(buckets, 1, 512, "the time buckets"), _what_code(what)
+
+
+class _TimelineAsk(NamedTuple):
+    """The timeline keyword with one of its options (evidence_request): B, timeline_q, timeline_what."""
+    buckets: object
+    q: object
+    what: object
+
+
+def _timeline_params(v):
+    """The timeline kind's parameters: {"buckets": B} for the keyword alone; with timeline_q / timeline_what
+    (a _TimelineAsk) also "q" (a float64 vector, _latency_args' rules) and / or "what"."""
+    if not isinstance(v, _TimelineAsk):
+        return {"buckets": _timeline_args(v)[0]}
+    params = {"buckets": _timeline_args(v.buckets, v.what)[0]}
+    if v.q is not None:
+        params["q"] = _latency_args(v.q, v.what)[0].copy()
+        params["q"].setflags(write=False)   # (the request is read-only)
+    if v.what != "self":
+        params["what"] = v.what
+    return params
 
 
 def _call_m(m):
@@ -254,7 +277,26 @@ def windows_timeline(ctx, windows, ops, *, buckets=30, what="self", origin=None,
     (INT64_MIN, INT64_MAX) needs both.  An empty window (rank_windows' status MR_ERR_VALUE) answers zeros.
     ValueError for buckets outside 1..512, an unknown what, more than 64 ops in a window, a width <= 0 or
     len(ops) != len(windows); tables without trace-level times, self time on a trace shard and -1 on a
-    trace shard are not covered (RuntimeError from the library)."""
+    trace shard are not covered (RuntimeError from the library).
+    windows_timeline_q is this call with latency quantiles per bucket."""
+    return _windows_timeline(ctx, windows, ops, buckets, what, origin, width, None, "linear")
+
+
+def windows_timeline_q(ctx, windows, ops, *, q=(0.5, 0.99), buckets=30, what="self", origin=None, width=None,
+                       method="linear"):
+    """windows_timeline with the latency quantiles of every bucket and side (mr_windows_timeline_q: one selection
+    of packed keys and ONE sort per chunk of windows): a percentile SLO laid over the timeline.  ``q``: a float in
+    [0, 1] or up to 16 of them; ``method``: 'linear', 'lower' or 'higher'.  Each answer is windows_timeline's dict
+    for the same arguments, and gains "q": float64[n_q] and "quantile": float64[B, 2, n_q] -- np.quantile of the
+    values counted in ``cnt`` (side 0 normal, 1 abnormal), in raw duration units, 0.0 where ``cnt`` is 0; the spans
+    before / after the bucket range get none.  A bad q or method is a ValueError before any device work; values
+    whose range takes more bits than a 64-bit key holds beside the class are a ValueError from the library."""
+    qv, _, mcode = _latency_args(q, what, method)
+    return _windows_timeline(ctx, windows, ops, buckets, what, origin, width, qv, mcode)
+
+
+def _windows_timeline(ctx, windows, ops, buckets, what, origin, width, qv, mcode):
+    """windows_timeline (qv None) / windows_timeline_q (qv, mcode: _latency_args')."""
     b, wcode = _timeline_args(buckets, what)
     n = len(windows)
     asked, k, cod, n_ops = _asked_args(ops, n)
@@ -272,16 +314,23 @@ def windows_timeline(ctx, windows, ops, *, buckets=30, what="self", origin=None,
     cnt, tot, mx = (np.zeros((n, k, b, 2), np.int64) for _ in range(3))
     out = np.zeros((n, k, 2, 2), np.int64)
     status = np.zeros(n, np.int32)
-    ctx.check(_lib.load().mr_windows_timeline(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
-                                              ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, wcode, ptr(b0, C.c_int64),
-                                              ptr(bw, C.c_int64), b, ptr(cnt, C.c_int64), ptr(tot, C.c_int64),
-                                              ptr(mx, C.c_int64), ptr(out, C.c_int64), ptr(status, C.c_int32)),
-              "mr_windows_timeline")
+    lead = (ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok, ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k,
+            wcode, ptr(b0, C.c_int64), ptr(bw, C.c_int64), b)
+    outs = (ptr(cnt, C.c_int64), ptr(tot, C.c_int64), ptr(mx, C.c_int64), ptr(out, C.c_int64))
+    if qv is None:
+        ctx.check(_lib.load().mr_windows_timeline(*lead, *outs, ptr(status, C.c_int32)), "mr_windows_timeline")
+    else:
+        tq = np.zeros((n, k, b, 2, qv.size), np.float64)
+        ctx.check(_lib.load().mr_windows_timeline_q(*lead, ptr(qv, C.c_double), qv.size, mcode, *outs, ptr(tq, C.c_double),
+                                                    ptr(status, C.c_int32)), "mr_windows_timeline_q")
     res = []
     for i in range(n):
         start = b0[i] + np.arange(b, dtype=np.int64) * bw[i]   # (int64 that wraps, for grids past the int64 range)
         res.append({c: {"start": start, "cnt": cnt[i, j].copy(), "sum": tot[i, j].copy(), "max": mx[i, j].copy(),
                         "out": out[i, j].copy()} for j, c in enumerate(asked[i])})
+        if qv is not None:
+            for j, c in enumerate(asked[i]):
+                res[i][c].update(q=qv.copy(), quantile=tq[i, j].copy())
     return res
 
 
@@ -355,7 +404,8 @@ def _call_row(table, r):
 
 
 def _timeline_row(table, r):
-    """A slot of windows_timeline's answer as plain lists of Python ints."""
+    """A slot of windows_timeline's answer as plain lists of Python ints ("q" and "quantile", where the answer
+    has them: lists of floats)."""
     return {k: v.tolist() for k, v in r.items()}
 
 
@@ -457,9 +507,21 @@ def window_timeline(data, start_time, end_time, slo, ops, *, buckets=30, what="s
     """windows_timeline for one window by names: {-1: the window's own traces, pod-op: ...} for the pod-ops
     of ``ops`` (names, or codes), each {"start", "cnt", "sum", "max", "out"} as plain lists of ints over the
     default buckets (origin = the window's start, width = (end - start) // buckets + 1 ns).  An op that is
-    no pod-op of the table raises ValueError; ops past the call's 64 slots go in further calls."""
+    no pod-op of the table raises ValueError; ops past the call's 64 slots go in further calls.
+    window_timeline_q is this call with latency quantiles per bucket."""
     return _one_window(windows_timeline, (-1,), {"buckets": _timeline_args(buckets, what)[0], "what": what},
                        _timeline_row, data, start_time, end_time, slo, ops, ctx, table, dev)
+
+
+def window_timeline_q(data, start_time, end_time, slo, ops, *, q=(0.5, 0.99), buckets=30, what="self", method="linear",
+                      ctx=None, table=None, dev=None):
+    """windows_timeline_q for one window by names: window_timeline's dict for the same arguments, each slot with
+    "q" and "quantile" ([bucket][side][q], raw duration units) as lists of floats.  A bad q is a ValueError before
+    any device work."""
+    params = {"q": _latency_args(q, what, method)[0], "buckets": _timeline_args(buckets, what)[0], "what": what,
+              "method": method}
+    return _one_window(windows_timeline_q, (-1,), params, _timeline_row, data, start_time, end_time, slo, ops, ctx, table,
+                       dev)
 
 
 def window_replicas(data, start_time, end_time, slo, ops, *, m=8, what="self", ctx=None, table=None, dev=None):
@@ -545,6 +607,27 @@ def _write_timeline(top_list, score_list, rows):
                 continue
             for b, (start, cnt, tot, mx) in enumerate(zip(r["start"], r["cnt"], r["sum"], r["max"])):   # ([normal, abnormal])
                 w.writerow([label, rank, b, int(start), int(cnt[1]), int(cnt[0])] + _mean_max(cnt[::-1], tot[::-1], mx[::-1]))
+    if any("quantile" in r for r in rows.values()):
+        _write_timeline_q(top_list, score_list, rows)
+
+
+def _write_timeline_q(top_list, score_list, rows):
+    """timeline_q.csv beside timeline.csv, from rows that carry quantiles (window_timeline's with q): the window's
+    own block first (``result`` = ``*``, rank 0), then each op of result.csv, in its order; per time bucket the
+    normal and then the abnormal side, one row per q: ``spans`` the rows (for ``*``: traces) that start in the
+    bucket on that side and ``value`` the q-quantile of their values, in the SLO's unit and rounding as
+    latency.csv's (0.0 for no rows).  Every bucket is written."""
+    with open("timeline_q.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "bucket", "start", "side", "spans", "q", "value"])
+        for rank, (label, key) in enumerate([("*", -1)] + [(service, service) for service, _ in _ranked(top_list, score_list)]):
+            r = rows.get(key)
+            if r is None or "quantile" not in r:
+                continue
+            for b, (start, cnt, quant) in enumerate(zip(r["start"], r["cnt"], r["quantile"])):   # ([normal, abnormal])
+                for side, name in enumerate(("normal", "abnormal")):
+                    for qj, v in zip(r["q"], _latency_ms(quant[side])):
+                        w.writerow([label, rank, b, int(start), name, int(cnt[side]), float(qj), float(v)])
 
 
 def _write_replicas(top_list, score_list, rows):
@@ -574,7 +657,8 @@ class Kind:
     window by names) take; ``lead`` is the pseudo-op asked in front of a window's top list; ``row`` maps a
     slot of the batch answer (table, slot) to what ``window`` gives for an op, and ``write`` puts such rows
     into the kind's file.  ``head`` names a parameter that the sweep plan keeps ahead of its answers and that
-    the writer takes after the rows (latency's q)."""
+    the writer takes after the rows (latency's q).  ``quantiles``: the (batch, window) forms that take the
+    parameters when an option of the keyword put a "q" among them (timeline_q), where the kind has such forms."""
     keyword: str
     key: str
     check: Callable
@@ -584,6 +668,15 @@ class Kind:
     row: Callable
     write: Callable
     head: str | None = None
+    quantiles: tuple | None = None
+
+    def batch_for(self, params):
+        """The batch entry that takes ``params``."""
+        return self.quantiles[0] if self.quantiles is not None and "q" in params else self.batch
+
+    def window_for(self, params):
+        """The one-window form that takes ``params``."""
+        return self.quantiles[1] if self.quantiles is not None and "q" in params else self.window
 
     def names(self, table, rows):
         """One window's batch answer {code: slot} as the writer's rows: by pod-op name where the table has names
@@ -611,8 +704,9 @@ KINDS = (
          _kind_row, _write_kinds),
     Kind("call_edges", "calls", lambda m: {"m": _call_m(m)}, (), windows_call_edges, window_calls, _call_row,
          _write_calls),
-    Kind("timeline", "timeline", lambda b: {"buckets": _timeline_args(b)[0]}, (-1,), windows_timeline, window_timeline,
-         _timeline_row, _write_timeline),
+    Kind("timeline", "timeline", _timeline_params, (-1,), windows_timeline, window_timeline, _timeline_row,
+         _write_timeline, quantiles=(windows_timeline_q, window_timeline_q)),   # (its value: the keyword, or a
+    # _TimelineAsk with timeline_q / timeline_what)
     Kind("replicas", "replicas", lambda m: {"m": _replica_args(m)[0]}, (), windows_replicas, window_replicas,
          _replica_row, _write_replicas),
 )
@@ -630,12 +724,18 @@ NOTHING = Evidence()
 
 
 def evidence_request(*, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                     call_edges=None, timeline=None, replicas=None):
+                     call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
     """The drivers' evidence keywords (online_anomaly_detect_RCA's docstring has each) checked into one
-    Evidence; ValueError for a bad one, before any device work.  None means "not asked"."""
+    Evidence; ValueError for a bad one, before any device work.  None means "not asked".  timeline_q and
+    timeline_what are options of the timeline kind: its parameters are {"buckets": B} without them."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
+    _what_code(timeline_what)
+    if timeline_q is not None and timeline is None:
+        raise ValueError("timeline_q needs timeline (the number of time buckets)")
+    if timeline is not None and (timeline_q is not None or timeline_what != "self"):
+        timeline = _TimelineAsk(timeline, timeline_q, timeline_what)
     values = {"latency": None if latency is None else (latency, latency_what), "kind_breakdown": kind_breakdown,
               "call_edges": call_edges, "timeline": timeline, "replicas": replicas}
     kinds = tuple((k, MappingProxyType(k.check(values[k.keyword]))) for k in KINDS if values.get(k.keyword) is not None)

@@ -28,8 +28,8 @@ from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
 from .evidence import (NOTHING, _detect_state, _latency_ms, _ranked, _write_calls, _write_kinds,  # noqa: F401
                        _write_latency, _write_replicas, _write_timeline, evidence_request, op_latency, window_calls,
-                       window_kinds, window_replicas, window_timeline, windows_call_edges, windows_kind_breakdown,
-                       windows_latency, windows_replicas, windows_timeline)
+                       window_kinds, window_replicas, window_timeline, window_timeline_q, windows_call_edges,
+                       windows_kind_breakdown, windows_latency, windows_replicas, windows_timeline, windows_timeline_q)
 from .graph import check_converge_args, check_exemplar_kinds, check_exemplar_m, check_exemplar_ops
 from .pagerank import ITERATIONS, trace_pagerank
 from .preprocess_data import (PagerankGraph, SpanStream, _quantile_args, get_operation_duration_data, get_operation_slo,  # noqa: F401
@@ -165,7 +165,8 @@ def sweep_chain(plan):
 
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
-               latency_what="self", kind_breakdown=None, call_edges=None, timeline=None, replicas=None):
+               latency_what="self", kind_breakdown=None, call_edges=None, timeline=None, replicas=None, timeline_q=None,
+               timeline_what="self"):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     The evidence keywords are online_anomaly_detect_RCA's: each asked kind makes ONE batch call over the
@@ -173,12 +174,14 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     latency: plan["latency"] = (q, {m: windows_latency's dict});
     kind_breakdown: plan["kinds"] = {m: windows_kind_breakdown's dict}, the whole window (None) first;
     call_edges: plan["calls"] = {m: windows_call_edges' dict};
-    timeline: plan["timeline"] = {m: windows_timeline's dict}, the window's own traces (-1) first;
+    timeline: plan["timeline"] = {m: windows_timeline's dict}, the window's own traces (-1) first -- with
+    timeline_q its slots carry "q" and "quantile" too, and timeline_what chooses their value;
     replicas: plan["replicas"] = {m: windows_replicas' dict}."""
     return _sweep_rank(plan, events, precision, iters,
                        evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                         latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
-                                        timeline=timeline, replicas=replicas))
+                                        timeline=timeline, replicas=replicas, timeline_q=timeline_q,
+                                        timeline_what=timeline_what))
 
 
 def _sweep_rank(plan, events, precision, iters, evidence):
@@ -194,7 +197,7 @@ def _sweep_rank(plan, events, precision, iters, evidence):
     ranked = rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=evidence.exemplars,
                           exemplar_kinds=evidence.exemplar_kinds)
     for kind, params in evidence.kinds:
-        answer = kind.batch(plan["ctx"], wins, [list(kind.lead) + r[0].tolist() for r in ranked], **params)
+        answer = kind.batch_for(params)(plan["ctx"], wins, [list(kind.lead) + r[0].tolist() for r in ranked], **params)
         plan[kind.key] = kind.plan_value(params, dict(zip(todo, answer)))
     return dict(zip(todo, ranked))
 
@@ -268,7 +271,7 @@ def _sweep_emit(plan, events, results, evidence):
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
                               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                              call_edges=None, timeline=None, replicas=None):
+                              call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -327,6 +330,14 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     tables whose window times vary within a trace are not covered (the call raises).  stdout and
     result.csv do not change; without it no file is written.
 
+    timeline_q (with timeline): a q as latency's: every trigger also rewrites ``timeline_q.csv`` beside
+    timeline.csv (columns result, rank, bucket, start, side, spans, q, value): the ``*`` block first, then each
+    op of result.csv, in its order; per bucket the normal and then the abnormal side, one row per q -- ``spans``
+    the bucket's count on that side, ``value`` the q-quantile of those spans' values (np.quantile, linear; the
+    SLO's unit and rounding; 0.0 for no spans): a percentile SLO laid over the timeline.  timeline.csv does not
+    change.  timeline_what: "self" or "duration", the value of an op's span in both files (the ``*`` block is
+    endTime - startTime either way).  timeline_q without timeline is a ValueError.
+
     replicas: an integer m (1..32): every trigger also rewrites ``replicas.csv`` beside result.csv
     (columns result, rank, pod, is_result, count_abnormal, count_normal, mean_abnormal, mean_normal,
     max_abnormal, max_normal, live, replicas): is it the pod, or the operation?  For each op of result.csv,
@@ -339,7 +350,7 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     check_converge_args(0.0, iters, 1)
     evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                 latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
-                                timeline=timeline, replicas=replicas)
+                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what)
     window_normal = pd.Timedelta(minutes=5)
     window_abnormal = pd.Timedelta(minutes=4)
     start = data["startTime"].min()
@@ -384,7 +395,8 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
                                         distinct_kinds=evidence.exemplar_kinds) if top_list else {}
                 _write_exemplars(top_list, score_list, rows, evidence.exemplar_kinds)
             for kind, params in evidence.kinds:
-                kind.file(top_list, score_list, kind.window(data, start_time, end_time, slo, top_list, **params), params)
+                kind.file(top_list, score_list, kind.window_for(params)(data, start_time, end_time, slo, top_list, **params),
+                          params)
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -403,18 +415,20 @@ class RCAStream:
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's.  The evidence keywords
     are its keywords too, each file rewritten at every trigger: exemplars, exemplar_kinds (exemplars.csv);
     latency, latency_what (latency.csv); kind_breakdown (kinds.csv); call_edges (calls.csv); timeline
-    (timeline.csv); replicas (replicas.csv).  They are kept checked, as one request, in ``evidence``."""
+    (timeline.csv), timeline_q (timeline_q.csv), timeline_what; replicas (replicas.csv).  They are kept
+    checked, as one request, in ``evidence``."""
 
     WINDOW = pd.Timedelta(minutes=5)
     STEP_ABNORMAL = pd.Timedelta(minutes=4)
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
                  exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-                 timeline=None, replicas=None):
+                 timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
         check_converge_args(0.0, iters, 1)
         self.evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                          latency_what=latency_what, kind_breakdown=kind_breakdown,
-                                         call_edges=call_edges, timeline=timeline, replicas=replicas)
+                                         call_edges=call_edges, timeline=timeline, replicas=replicas,
+                                         timeline_q=timeline_q, timeline_what=timeline_what)
         self.slo, self.operation_list, self.iters = slo, operation_list, iters
         self.ctx = ctx or _lib.default_context()
         self.data = None          # retained spans as a DataFrame (host mode only)
@@ -577,7 +591,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
                exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-               timeline=None, replicas=None):
+               timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -597,12 +611,14 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     latency (with latency_what): ``"latency"``, op_latency's dict;
     kind_breakdown: ``"kinds"``, window_kinds' dict -- the whole window (key None), then the ops;
     call_edges: ``"calls"``, window_calls' dict;
-    timeline: ``"timeline"``, window_timeline's dict -- the window's own traces (key -1), then the ops;
+    timeline: ``"timeline"``, window_timeline's dict -- the window's own traces (key -1), then the ops; with
+    timeline_q (a q as latency's) every slot carries ``"q"`` and ``"quantile"`` ([bucket][side][q], raw duration
+    units) too, and timeline_what ("self" or "duration") chooses the value of an op's span;
     replicas: ``"replicas"``, window_replicas' dict."""
     tol = _iter_args(iters, tol, check_every, info, dict)
     evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                 latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
-                                timeline=timeline, replicas=replicas)
+                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what)
     exemplars = evidence.exemplars
     ctx = ctx or _lib.default_context()
     if table is None or dev is None:
@@ -634,7 +650,8 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
                                             precision=precision, ctx=ctx, table=table, dev=dev,
                                             distinct_kinds=evidence.exemplar_kinds) if m else {}
     for kind, params in evidence.kinds:
-        res[kind.key] = kind.window(data, start_time, end_time, slo, res["top"], ctx=ctx, table=table, dev=dev, **params)
+        res[kind.key] = kind.window_for(params)(data, start_time, end_time, slo, res["top"], ctx=ctx, table=table, dev=dev,
+                                                **params)
     return res
 
 
