@@ -795,6 +795,69 @@ int mr_windows_replicas(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* s
                         int64_t* rp_own, int64_t* rp_tot /*[n_windows * K * 2 * 3]: window, entry, side, {cnt, sum, max}*/,
                         int32_t* status /*[n_windows]*/);
 
+/* ------------------------------------------------------------------ endpoint evidence
+ * Which user-facing endpoints are hit, and through which of them does the anomaly reach a suspect op?
+ * "POST /preserve has 412 abnormal traces of 430, GET /stations 0 of 9800"; "every abnormal trace through
+ * order_query entered at preserve".  The kind breakdown splits one endpoint into dozens of exact op sets and
+ * never names it; this entry groups a window's traces by their ENTRY operation.  It is the first evidence that
+ * counts DISTINCT TRACES per op.  No reference counterpart.
+ * Per table, independent of the window:
+ *   Root row: a row r with parent[r] < 0 -- its ParentSpanId is null or is no spanID of the table.
+ *   Entry row of trace t: among t's root rows the one with the largest duration, compared as int64; ties go to
+ *   the smallest row position in the table.
+ *   Endpoint of t: podop[entry row]; MR_EP_NONE (-2) when t has no root row (a parent cycle, or every parent
+ *   resolving to another trace's span).
+ *   Value of t: d(t) = tend - tstart at trace level, as the int64 it wraps to.
+ *   Endpoint universe: the table's distinct endpoints in pod-op code order, MR_EP_NONE last.
+ * The endpoints are computed at the first call on a table and kept with it; mr_spans_entry_ops copies them out:
+ * ep[t], t < n_traces, the endpoint's pod-op code or MR_EP_NONE.
+ * Window i = spans[i], [t0[i], t1[i]], a3[i] / a3_valid[i] as in mr_windows_kind_breakdown; its partition is that
+ * window's mr_detect state (0 not counted, 1 normal, 2 abnormal), computed on the device and never copied out;
+ * side 0 is normal, side 1 abnormal.
+ * Asked slots: podops[i * K + j], j < n_ops[i].  -1 selects every trace of the window (state 1 or 2); a pod-op
+ * code p >= 0 selects the traces with AT LEAST ONE row of pod-op p -- each trace once, however many spans of p
+ * it holds.  Per slot, endpoint E and side:
+ *   cnt  the selected traces whose endpoint is E
+ *   sum  the sum of d(t) over them (uint64 that wraps, given as int64)
+ *   max  the largest d(t), 0 where cnt is 0
+ * An endpoint is LIVE in a slot when cnt[0] + cnt[1] > 0.  The live endpoints are ordered by abnormal count
+ * descending, then normal count ascending, then code ascending with MR_EP_NONE last: a total order.
+ * Outputs, window i, asked entry j (x = i * K + j):
+ *   ep_op[x * m + e]                                  the first min(m, live) endpoints: a pod-op code or MR_EP_NONE; -1 padded
+ *   ep_cnt / ep_sum / ep_max[(x * m + e) * 2 + side]  their numbers, 0 padded
+ *   ep_n[x]     the number of entries
+ *   ep_live[x]  the live endpoints
+ *   ep_tot[(x * 2 + side) * 3 + {cnt, sum, max}]      the numbers over ALL live endpoints: for -1 the window's
+ *               traces of that side, for an op its trace coverage
+ *   status[i]   MR_OK, or MR_ERR_VALUE for an empty window (T2), whose outputs are the padding
+ * The padding: ep_op -1, everything else 0.  A slot asked twice is answered each time; an op with no trace in
+ * the window and entries j >= n_ops[i] answer the padding.
+ * Every output is an integer sum, an integer maximum or a place in a total order, so the answer is the same
+ * bits under any cut into blocks, any chunking of the call's windows (MR_EP_CHUNK / MR_EP_BLOCKS, read per call,
+ * force a cut), any place of a window in the call and any neighbours.  One count launch answers a chunk of
+ * windows, never a launch per op or per endpoint.  The ranking entries are untouched and no ranking state is read.
+ * MR_ERR_ARG: a null pointer, K outside 1..64, m outside 1..32, n_ops[i] outside 0..K, a code outside
+ * [-1, n_podops), a table of another context.
+ * MR_ERR_STATE, tested in this order, the message naming which: a table without the per-trace index (its key
+ * bits did not fit, or it is empty: its per-trace distinct pod-op lists are what an op slot reads); a table
+ * without trace-level times (no startTime / endTime columns, or times that vary within a trace: d(t) is the
+ * trace's); a trace shard of a larger table (cols.row set: a parent may lie on another rank, so a local root
+ * need not be a root; mr_spans_entry_ops refuses it too); a window whose slots times (endpoints + 1) reach 2^30
+ * (a counter's key is an int32).  There is no fallback for any of them.
+ * An argument error or a state error leaves the context usable. */
+#define MR_EP_NONE (-2)
+int mr_spans_entry_ops(mr_ctx* ctx, const mr_spans* s, int32_t* ep /*[n_traces]: endpoint pod-op code or MR_EP_NONE*/);
+int mr_windows_endpoints(mr_ctx* ctx, int32_t n_windows, const mr_spans* const* spans, const int64_t* t0,
+                         const int64_t* t1, const double* const* a3, const uint8_t* const* a3_valid,
+                         const int32_t* podops /*[n_windows * K], -1 = the window's traces*/, const int32_t* n_ops,
+                         int32_t K /*1..64*/, int32_t m /*1..32*/,
+                         int32_t* ep_op /*[n_windows * K * m] endpoint code, MR_EP_NONE, or -1 padding*/,
+                         int64_t* ep_cnt, int64_t* ep_sum,
+                         int64_t* ep_max /*[n_windows * K * m * 2]: window, entry, endpoint, side; 0 padded*/,
+                         int32_t* ep_n, int32_t* ep_live /*[n_windows * K]*/,
+                         int64_t* ep_tot /*[n_windows * K * 2 * 3]: window, entry, side, {cnt, sum, max}*/,
+                         int32_t* status /*[n_windows]*/);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
  * One process per GPU.  The unique id (128 bytes) is produced by rank 0 and broadcast by the
  * caller (torch.distributed / any host channel).  Used by the trace-sharded PageRank. */

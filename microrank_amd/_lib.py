@@ -25,6 +25,7 @@ QUANTILE_METHODS = {"linear": MR_Q_LINEAR, "lower": MR_Q_LOWER, "higher": MR_Q_H
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1   # mr_slo_quantiles: t0 / t1 of "the whole table"
 MR_LAT_DURATION, MR_LAT_SELF = 0, 1   # mr_op_latency / mr_windows_latency: the value of a row
 LATENCY_VALUES = {"duration": MR_LAT_DURATION, "self": MR_LAT_SELF}
+MR_EP_NONE = -2   # mr_spans_entry_ops / mr_windows_endpoints: the endpoint of a trace without a root row
 
 SPECTRUM_METHODS = ("dstar2", "ochiai", "jaccard", "sorensendice", "m1", "m2", "goodman", "tarantula",
                     "russellrao", "hamann", "dice", "simplematcing", "rogers")
@@ -156,6 +157,11 @@ SIGNATURES = {
     "mr_windows_replicas": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, C.c_int, i32p, i64p, i64p,
                                       i64p, i32p, i32p, i32p, i32p, i64p, i64p, i32p]),
+    # endpoint evidence: every trace's entry operation, and many windows' traces grouped by it per asked pod-op
+    "mr_spans_entry_ops": (C.c_int, [P, P, i32p]),
+    "mr_windows_endpoints": (C.c_int, [P, C.c_int32, C.POINTER(P), i64p, i64p, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), i32p, i32p, C.c_int32, C.c_int32, i32p, i64p, i64p, i64p,
+                                       i32p, i32p, i64p, i32p]),
     "mr_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "mr_comm_init": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "mr_comm_allreduce_f64": (C.c_int, [P, P, C.c_int64, C.c_int]),

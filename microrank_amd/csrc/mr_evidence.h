@@ -1,8 +1,9 @@
 // What the evidence entries over a list of windows share (mr_windows_latency, _kind_breakdown, _call_edges,
-// _timeline; the list pieces also serve mr_exemplar.hip).  Host: the checks of the nine leading arguments,
-// the call's SLO uploads, a window's detector partition, the asked codes' slots, the chunk cut, the
-// list-block plan and the one pinned read-back.  Device: the block's counter table in LDS that
-// k_ce_count and k_tl_count keep.  An entry keeps what differs for a reason: its own requirements of a
+// _timeline, _replicas, _endpoints; the list pieces also serve mr_exemplar.hip).  Host: the checks of the nine
+// leading arguments, the call's SLO uploads, a window's detector partition, the asked codes' slots, the chunk
+// cut, the list-block plan and the one pinned read-back.  Device: the block's counter table in LDS that
+// k_ce_count, k_tl_count, k_rp_count and k_ep_count keep, and the selection of a slot's first m live entries
+// that k_rp_select and k_ep_select run.  An entry keeps what differs for a reason: its own requirements of a
 // table (MR_ERR_STATE), its device descriptor, its kernels, its read-back layout and its scatter loop.
 #pragma once
 #include <cstring>
@@ -243,3 +244,124 @@ struct EvTable {
             if (direct ? n[i] != 0ull : k[i] != 0ull) ev_add(cnt, direct ? (K)i : (K)(k[i] - 1ull), EvRun{n[i], s[i], m[i]});
     }
 };
+
+// ---------------------------------------------------------------- a slot's selection (device)
+// What k_rp_select (mr_replicas.hip) and k_ep_select (mr_endpoints.hip) share: a slot's R dense counters of six
+// words -- side 0's {n, sum, biased max}, then side 1's -- its live count, its totals, and the first m live
+// entries under the order (abnormal count descending, normal count ascending, place q ascending).
+// A live entry's place in the order; q < 0: none
+struct EvKey {
+    unsigned long long ca, cn;
+    int32_t q;
+};
+__device__ __forceinline__ bool ev_before(const EvKey& a, const EvKey& b) {
+    return a.ca != b.ca ? a.ca > b.ca : a.cn != b.cn ? a.cn < b.cn : a.q < b.q;
+}
+__device__ __forceinline__ EvKey ev_better(const EvKey a, const EvKey b) {
+    const bool pa = b.q < 0 || (a.q >= 0 && ev_before(a, b));   // (field by field: selects, no addresses)
+    return EvKey{pa ? a.ca : b.ca, pa ? a.cn : b.cn, pa ? a.q : b.q};
+}
+// a counter's maximum as the answer gives it: un-biased, 0 where the count is 0
+__device__ __forceinline__ unsigned long long ev_max_of(unsigned long long n, unsigned long long mx) {
+    return n ? mx ^ EV_BIAS : 0ull;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long x = __shfl_xor(v, o, WAVE);
+        v = x > v ? x : v;
+    }
+    return v;
+}
+constexpr int EV_SW = 8;   // a selection record: live, n, tot[2][3], then m entries of 7 words
+// A block of T threads (every thread calls it) selects over c[R * 6]: rec[0] live, rec[1] n = min(m, live),
+// rec[2 .. 8) the totals (side, {cnt, sum, max}), then n entries of 7 words: code_of(q), its (cnt, sum, max) on
+// side 0 and on side 1.  The live count, the totals, then m rounds of a block-wide best-of-rest; the two counts
+// are compared as they are -- no packed key -- so the order is exact for any count.  tot[7] and wbest[T / WAVE]
+// are the block's shared words.
+template <int T, class CodeOf>
+__device__ __forceinline__ void ev_select_block(const unsigned long long* __restrict__ c, int32_t R,
+                                                unsigned long long* __restrict__ rec, int32_t m, CodeOf code_of,
+                                                unsigned long long* tot, EvKey* wbest) {
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    if (threadIdx.x < 7) tot[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long lv = 0ull, c0 = 0ull, s0 = 0ull, x0 = 0ull, c1 = 0ull, s1 = 0ull, x1 = 0ull;   // live; {cnt, sum, biased max} of side 0, 1
+    for (int32_t q = (int32_t)threadIdx.x; q < R; q += T) {
+        const unsigned long long* p = c + (size_t)q * 6;
+        lv += p[0] + p[3] > 0ull;
+        c0 += p[0];
+        s0 += p[1];
+        x0 = p[2] > x0 ? p[2] : x0;
+        c1 += p[3];
+        s1 += p[4];
+        x1 = p[5] > x1 ? p[5] : x1;
+    }
+    lv = wave_sum_u64(lv);
+    c0 = wave_sum_u64(c0);
+    s0 = wave_sum_u64(s0);
+    x0 = wave_max_u64(x0);
+    c1 = wave_sum_u64(c1);
+    s1 = wave_sum_u64(s1);
+    x1 = wave_max_u64(x1);
+    if (lane == 0) {
+        atomicAdd(&tot[0], lv);
+        atomicAdd(&tot[1], c0);
+        atomicAdd(&tot[2], s0);
+        atomicMax(&tot[3], x0);
+        atomicAdd(&tot[4], c1);
+        atomicAdd(&tot[5], s1);
+        atomicMax(&tot[6], x1);
+    }
+    __syncthreads();
+    const unsigned long long live = tot[0];
+    const int32_t n = (int32_t)(live < (unsigned long long)m ? live : (unsigned long long)m);
+    if (threadIdx.x == 0) {
+        rec[0] = live;
+        rec[1] = (unsigned long long)n;
+        rec[2] = tot[1];
+        rec[3] = tot[2];
+        rec[4] = ev_max_of(tot[1], tot[3]);
+        rec[5] = tot[4];
+        rec[6] = tot[5];
+        rec[7] = ev_max_of(tot[4], tot[6]);
+    }
+    EvKey last{0ull, 0ull, -1};
+    for (int32_t e = 0; e < n; ++e) {   // (block-uniform: n <= live, so every round finds an entry)
+        EvKey best{0ull, 0ull, -1};
+        for (int32_t q = (int32_t)threadIdx.x; q < R; q += T) {
+            const EvKey k{c[(size_t)q * 6 + 3], c[(size_t)q * 6], q};
+            if (k.ca + k.cn == 0ull) continue;
+            if (last.q >= 0 && !ev_before(last, k)) continue;   // (listed already)
+            best = ev_better(best, k);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const EvKey x{__shfl_xor(best.ca, o, WAVE), __shfl_xor(best.cn, o, WAVE), __shfl_xor(best.q, o, WAVE)};
+            best = ev_better(best, x);
+        }
+        __syncthreads();   // (the round before has read wbest)
+        if (lane == 0) wbest[wv] = best;
+        __syncthreads();
+        best = wbest[0];
+#pragma unroll
+        for (int i = 1; i < T / WAVE; ++i) best = ev_better(best, wbest[i]);
+        last = best;
+        if (threadIdx.x == 0 && best.q >= 0) {
+            const unsigned long long* p = c + (size_t)best.q * 6;
+            unsigned long long* o = rec + EV_SW + (size_t)e * 7;
+            o[0] = (unsigned long long)(long long)code_of(best.q);
+            o[1] = p[0];
+            o[2] = p[1];
+            o[3] = ev_max_of(p[0], p[2]);
+            o[4] = p[3];
+            o[5] = p[4];
+            o[6] = ev_max_of(p[3], p[5]);
+        }
+    }
+}

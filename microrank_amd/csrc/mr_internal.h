@@ -464,6 +464,14 @@ struct mr_spans {
     mutable std::vector<int32_t> rp_sv_h, rp_off_h;
     mutable int rp_state = 0;
     mutable int32_t rp_bad[3] = {0, 0, 0};
+    // endpoint evidence (mr_endpoints.hip): the entry operation of every trace, built by the first
+    // mr_spans_entry_ops / mr_windows_endpoints call on this table and kept: ep[t] the pod-op of trace t's entry
+    // row (MR_EP_NONE: no root row), ep_rank[p] the place of pod-op p among the table's distinct endpoints in code
+    // order (-1: no trace enters at p), ep_code[] those endpoints, ep_tr[t] = ep_rank[ep[t]] (ep_R for
+    // MR_EP_NONE: the last key of a slot), ep_R the host's copy of their number.  Nothing else reads or writes them.
+    mutable DBuf<int32_t> ep, ep_rank, ep_code, ep_tr;
+    mutable int32_t ep_R = 0;
+    mutable bool ep_ok = false;
 };
 
 int mr_spans_index(mr_ctx* ctx, mr_spans* s);

@@ -45,7 +45,7 @@ constexpr int RP_TILE = RP_T * RP_U;          // rows of a block's tile
 constexpr int RP_MAXOPS = 64;                 // asked slots per window (the evidence entries' limit)
 constexpr int RP_MAXM = 32;                   // listed replicas per asked entry
 constexpr int RP_MAX_CB = 4096;               // row blocks per window (grid-stride over the tiles)
-constexpr int RP_SW = 8;                      // a slot's selection record: live, n, tot[2][3], then m entries of 7 words
+constexpr int RP_SW = EV_SW;                  // a slot's selection record (mr_evidence.h ev_select_block)
 constexpr int64_t RP_MAX_KEYS = (int64_t)1 << 30;   // replicas of a window's slots: key = replica * 2 + side is an int32
 
 struct RpWin {
@@ -264,124 +264,17 @@ __global__ void __launch_bounds__(RP_T) k_rp_count(const RpWin* __restrict__ ws)
 }
 
 // ---------------------------------------------------------------- selection
-// a live replica's place in the order: abnormal count descending, normal count ascending, place in its group
-// (= code) ascending; q < 0: none
-struct RpKey {
-    unsigned long long ca, cn;
-    int32_t q;
-};
-__device__ __forceinline__ bool rp_before(const RpKey& a, const RpKey& b) {
-    return a.ca != b.ca ? a.ca > b.ca : a.cn != b.cn ? a.cn < b.cn : a.q < b.q;
-}
-__device__ __forceinline__ RpKey rp_better(const RpKey a, const RpKey b) {
-    const bool pa = b.q < 0 || (a.q >= 0 && rp_before(a, b));   // (field by field: selects, no addresses)
-    return RpKey{pa ? a.ca : b.ca, pa ? a.cn : b.cn, pa ? a.q : b.q};
-}
-// a counter's maximum as the answer gives it: un-biased, 0 where the count is 0
-__device__ __forceinline__ unsigned long long rp_max_of(unsigned long long n, unsigned long long mx) {
-    return n ? mx ^ EV_BIAS : 0ull;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long x = __shfl_xor(v, o, WAVE);
-        v = x > v ? x : v;
-    }
-    return v;
-}
-
 // block (slot u, window): rec[0] live, rec[1] n = min(m, live), rec[2 .. 8) the totals (side, {cnt, sum, max}),
 // then n entries of 7 words: the replica's pod-op code, its (cnt, sum, max) on side 0 and on side 1
 __global__ void __launch_bounds__(RP_T) k_rp_select(const RpWin* __restrict__ ws, int32_t m) {
     __shared__ unsigned long long tot[7];
-    __shared__ RpKey wbest[RP_T / WAVE];
+    __shared__ EvKey wbest[RP_T / WAVE];
     const RpWin& w = ws[blockIdx.y];
     const int32_t u = (int32_t)blockIdx.x;
     if (u >= w.n_ops) return;   // (block-uniform)
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    const int32_t R = w.nr[u];
-    const unsigned long long* __restrict__ c = w.cnt + (size_t)w.base[u] * 6;
-    unsigned long long* __restrict__ rec = w.sel + (size_t)u * (RP_SW + 7 * m);
-    if (threadIdx.x < 7) tot[threadIdx.x] = 0ull;
-    __syncthreads();
-    unsigned long long lv = 0ull, c0 = 0ull, s0 = 0ull, x0 = 0ull, c1 = 0ull, s1 = 0ull, x1 = 0ull;   // live; {cnt, sum, biased max} of side 0, 1
-    for (int32_t q = (int32_t)threadIdx.x; q < R; q += RP_T) {
-        const unsigned long long* p = c + (size_t)q * 6;
-        lv += p[0] + p[3] > 0ull;
-        c0 += p[0];
-        s0 += p[1];
-        x0 = p[2] > x0 ? p[2] : x0;
-        c1 += p[3];
-        s1 += p[4];
-        x1 = p[5] > x1 ? p[5] : x1;
-    }
-    lv = wave_sum_u64(lv);
-    c0 = wave_sum_u64(c0);
-    s0 = wave_sum_u64(s0);
-    x0 = wave_max_u64(x0);
-    c1 = wave_sum_u64(c1);
-    s1 = wave_sum_u64(s1);
-    x1 = wave_max_u64(x1);
-    if (lane == 0) {
-        atomicAdd(&tot[0], lv);
-        atomicAdd(&tot[1], c0);
-        atomicAdd(&tot[2], s0);
-        atomicMax(&tot[3], x0);
-        atomicAdd(&tot[4], c1);
-        atomicAdd(&tot[5], s1);
-        atomicMax(&tot[6], x1);
-    }
-    __syncthreads();
-    const unsigned long long live = tot[0];
-    const int32_t n = (int32_t)(live < (unsigned long long)m ? live : (unsigned long long)m);
-    if (threadIdx.x == 0) {
-        rec[0] = live;
-        rec[1] = (unsigned long long)n;
-        rec[2] = tot[1];
-        rec[3] = tot[2];
-        rec[4] = rp_max_of(tot[1], tot[3]);
-        rec[5] = tot[4];
-        rec[6] = tot[5];
-        rec[7] = rp_max_of(tot[4], tot[6]);
-    }
-    RpKey last{0ull, 0ull, -1};
-    for (int32_t e = 0; e < n; ++e) {   // (block-uniform: n <= live, so every round finds a replica)
-        RpKey best{0ull, 0ull, -1};
-        for (int32_t q = (int32_t)threadIdx.x; q < R; q += RP_T) {
-            const RpKey k{c[(size_t)q * 6 + 3], c[(size_t)q * 6], q};
-            if (k.ca + k.cn == 0ull) continue;
-            if (last.q >= 0 && !rp_before(last, k)) continue;   // (listed already)
-            best = rp_better(best, k);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const RpKey x{__shfl_xor(best.ca, o, WAVE), __shfl_xor(best.cn, o, WAVE), __shfl_xor(best.q, o, WAVE)};
-            best = rp_better(best, x);
-        }
-        __syncthreads();   // (the round before has read wbest)
-        if (lane == 0) wbest[wv] = best;
-        __syncthreads();
-        best = wbest[0];
-#pragma unroll
-        for (int i = 1; i < RP_T / WAVE; ++i) best = rp_better(best, wbest[i]);
-        last = best;
-        if (threadIdx.x == 0 && best.q >= 0) {
-            const unsigned long long* p = c + (size_t)best.q * 6;
-            unsigned long long* o = rec + RP_SW + (size_t)e * 7;
-            o[0] = (unsigned long long)(long long)w.pods[w.rbeg[u] + best.q];
-            o[1] = p[0];
-            o[2] = p[1];
-            o[3] = rp_max_of(p[0], p[2]);
-            o[4] = p[3];
-            o[5] = p[4];
-            o[6] = rp_max_of(p[3], p[5]);
-        }
-    }
+    const int32_t* __restrict__ pods = w.pods + w.rbeg[u];
+    ev_select_block<RP_T>(w.cnt + (size_t)w.base[u] * 6, w.nr[u], w.sel + (size_t)u * (RP_SW + 7 * m), m,
+                          [pods](int32_t q) { return pods[q]; }, tot, wbest);
 }
 
 // the chunk's output planes, each in the entry's final layout over the chunk's windows
@@ -429,15 +322,15 @@ __global__ void __launch_bounds__(RP_T) k_rp_finish(const RpWin* __restrict__ ws
         }
     }
     const unsigned long long* mine = c + (size_t)rk * 6;
-    const RpKey me{mine[3], mine[0], rk};
+    const EvKey me{mine[3], mine[0], rk};
     const bool has = me.ca + me.cn > 0ull;
     if (threadIdx.x == 0) before = 0u;
     __syncthreads();
     if (has) {   // (block-uniform)
         unsigned int b = 0;
         for (int32_t q = (int32_t)threadIdx.x; q < R; q += RP_T) {
-            const RpKey k{c[(size_t)q * 6 + 3], c[(size_t)q * 6], q};
-            b += k.ca + k.cn > 0ull && rp_before(k, me);
+            const EvKey k{c[(size_t)q * 6 + 3], c[(size_t)q * 6], q};
+            b += k.ca + k.cn > 0ull && ev_before(k, me);
         }
         b = (unsigned int)wave_sum_u64(b);
         if ((threadIdx.x & (WAVE - 1)) == 0 && b) atomicAdd(&before, b);
@@ -445,7 +338,7 @@ __global__ void __launch_bounds__(RP_T) k_rp_finish(const RpWin* __restrict__ ws
     __syncthreads();
     if (threadIdx.x < 6) {
         const int f = threadIdx.x % 3, sd = threadIdx.x / 3;
-        o.own[x * 6 + threadIdx.x] = (long long)(f == 2 ? rp_max_of(mine[sd * 3], mine[sd * 3 + 2]) : mine[sd * 3 + f]);
+        o.own[x * 6 + threadIdx.x] = (long long)(f == 2 ? ev_max_of(mine[sd * 3], mine[sd * 3 + 2]) : mine[sd * 3 + f]);
         o.tot[x * 6 + threadIdx.x] = (long long)rec[2 + threadIdx.x];
     }
     if (threadIdx.x == 0) {

@@ -7,7 +7,9 @@ call order and ``evidence_request`` checks a caller's keywords into one request;
 ``online_rca`` loop over that request and never name a kind.  A new kind is one record in ``KINDS``, its
 keyword in ``evidence_request`` and in the four public signatures of ``online_rca``, and a docstring line.
 An option of a kind (the timeline's ``timeline_q`` / ``timeline_what``) is a keyword of ``evidence_request`` that
-ends up in that kind's parameters; ``Kind.batch_for`` / ``window_for`` pick the form that takes them.
+ends up in that kind's parameters; ``Kind.batch_for`` / ``window_for`` pick the form that takes them.  A second
+grouping of a kind (``kind_by="endpoint"``: the kind breakdown by entry operation) is such an option too: its forms,
+its key and its file are a record of ``Kind.variants``.
 """
 from __future__ import annotations
 
@@ -84,6 +86,26 @@ def _call_m(m):
 def _kind_m(m):
     """The kind_breakdown keyword / windows_kind_breakdown's m: an integer in 1..32, else ValueError."""
     return _int_in(m, 1, 32, "the kinds per op")
+
+
+def _endpoint_m(m):
+    """windows_endpoints' m (the kind_breakdown keyword with kind_by="endpoint"): an integer in 1..32, else
+    ValueError."""
+    return _int_in(m, 1, 32, "the endpoints per op")
+
+
+class _KindAsk(NamedTuple):
+    """The kind_breakdown keyword with its kind_by option (evidence_request): m, "endpoint"."""
+    m: object
+    by: str
+
+
+def _kind_params(v):
+    """The kind_breakdown kind's parameters: {"m": m} for the keyword alone (trace kinds); with
+    kind_by="endpoint" (a _KindAsk) {"m": m, "by": "endpoint"}: the traces grouped by entry operation."""
+    if not isinstance(v, _KindAsk):
+        return {"m": _kind_m(v)}
+    return {"m": _endpoint_m(v.m), "by": v.by}
 
 
 def _latency_args(q, what, method="linear"):
@@ -385,6 +407,48 @@ def windows_replicas(ctx, windows, ops, *, m=8, what="self"):
     return [{c: one(i, j) for j, c in enumerate(asked[i])} for i in range(n)]
 
 
+def windows_endpoints(ctx, windows, ops, *, m=8):
+    """Which user-facing endpoints are hit, and through which does the anomaly reach each op
+    (mr_windows_endpoints, csrc/mr_endpoints.hip)?  ``windows`` as rank_windows'; ``ops`` one sequence per window of
+    pod-op codes, None standing for the whole window.  A trace's endpoint is the pod-op of its entry row -- its
+    longest root span (no parent in the table), ties to the first row -- or None for a trace without a root row;
+    its value is endTime - startTime.  An op selects the traces with at least one of its spans, each ONCE.
+    Returns per window {code or None: {"entries": [(endpoint code or None, cnt_abn, cnt_nor, sum_abn, sum_nor,
+    max_abn, max_nor), ...], "live": int, "total": (6 ints, the entries' order)}}: ``entries`` the first m
+    endpoints among those with a selected trace -- most abnormal traces first, then fewest normal ones, then the
+    smallest code, None last -- with the traces on each side of the window's own detector partition, the sum
+    (int64, wrapping) and the largest of their values in raw time units (a max of no trace is 0); ``live`` the
+    endpoints with a selected trace and ``total`` the numbers over all of them.  An empty window (rank_windows'
+    status MR_ERR_VALUE) answers empty entries and zeros.  ValueError for m outside 1..32, more than 64 ops in a
+    window or len(ops) != len(windows); trace shards and tables without a per-trace index or trace-level times
+    are not covered (RuntimeError from the library)."""
+    m = _endpoint_m(m)
+    n = len(windows)
+    asked, k, cod, n_ops = _asked_args(ops, n, none_ok=True)
+    if n == 0:
+        return []
+    keep, spans, t0, t1, a3, ok = _window_args(windows)
+    eop = np.zeros((n, k, m), np.int32)
+    cnt, tot, mx = (np.zeros((n, k, m, 2), np.int64) for _ in range(3))
+    cn, live = np.zeros((n, k), np.int32), np.zeros((n, k), np.int32)
+    total = np.zeros((n, k, 2, 3), np.int64)
+    status = np.zeros(n, np.int32)
+    ctx.check(_lib.load().mr_windows_endpoints(ctx.h, n, spans, ptr(t0, C.c_int64), ptr(t1, C.c_int64), a3, ok,
+                                               ptr(cod, C.c_int32), ptr(n_ops, C.c_int32), k, m, ptr(eop, C.c_int32),
+                                               ptr(cnt, C.c_int64), ptr(tot, C.c_int64), ptr(mx, C.c_int64),
+                                               ptr(cn, C.c_int32), ptr(live, C.c_int32), ptr(total, C.c_int64),
+                                               ptr(status, C.c_int32)), "mr_windows_endpoints")
+    planes = [a[..., side].tolist() for a in (cnt, tot, mx) for side in (1, 0)]   # (abnormal before normal)
+    el, nl, ll = eop.tolist(), cn.tolist(), live.tolist()
+    tl = total[:, :, ::-1, :].transpose(0, 1, 3, 2).reshape(n, k, 6).tolist()
+
+    def one(i, j):
+        codes = [None if c == _lib.MR_EP_NONE else c for c in el[i][j][:nl[i][j]]]
+        return {"entries": list(zip(codes, *[p[i][j] for p in planes])), "live": ll[i][j], "total": tuple(tl[i][j])}
+
+    return [{c: one(i, j) for j, c in enumerate(asked[i])} for i in range(n)]
+
+
 # ------------------------------------------------------------------ answers in codes -> rows by name
 def _latency_row(table, r):
     """A slot of windows_latency's answer as op_latency gives it: the SLO's unit and rounding."""
@@ -413,6 +477,13 @@ def _replica_row(table, r):
     """A slot of windows_replicas' answer with the replicas' pod-op names where the table has them."""
     names = table.podop_names
     return dict(r, entries=[((names[e[0]] if names is not None else e[0]),) + e[1:] for e in r["entries"]])
+
+
+def _endpoint_row(table, r):
+    """A slot of windows_endpoints' answer with the endpoints' pod-op names where the table has them (None stays)."""
+    names = table.podop_names
+    return dict(r, entries=[((names[e[0]] if names is not None and e[0] is not None else e[0]),) + e[1:]
+                            for e in r["entries"]])
 
 
 # ------------------------------------------------------------------------------------ one-window forms
@@ -532,6 +603,15 @@ def window_replicas(data, start_time, end_time, slo, ops, *, m=8, what="self", c
                        start_time, end_time, slo, ops, ctx, table, dev)
 
 
+def window_endpoints(data, start_time, end_time, slo, ops, *, m=8, ctx=None, table=None, dev=None):
+    """windows_endpoints for one window by names: {None: the whole window, pod-op: {"entries", "live", "total"}}
+    for the pod-ops of ``ops`` (names, or codes), endpoints by pod-op name where the table has names (None: the
+    traces without a root row).  An op that is no pod-op of the table raises ValueError; ops past the call's 64
+    slots go in further calls."""
+    return _one_window(windows_endpoints, (None,), {"m": _endpoint_m(m)}, _endpoint_row, data, start_time, end_time,
+                       slo, ops, ctx, table, dev)
+
+
 # --------------------------------------------------------------------------------------------- writers
 def _ranked(top_list, score_list):
     """result.csv's order: (op, score) by score, best first, ties in top-list order."""
@@ -649,6 +729,26 @@ def _write_replicas(top_list, score_list, rows):
                            _mean_max(e[1:3], e[3:5], e[5:7]) + [int(r["live"]), int(r["all"])])
 
 
+def _write_endpoints(top_list, score_list, rows):
+    """endpoints.csv beside result.csv: the whole window's block first (``result`` = ``*``, rank 0), then for each
+    op of result.csv, in its order, the listed endpoints in answer order (rows: window_endpoints' dict), one row
+    per endpoint: the traces that enter there on each side of the detector's partition, the mean and the largest
+    of their endTime - startTime, then the slot's live endpoints.  The traces without a root row are written as
+    ``(none)``.  A mean is sum / count in float64 (0.0 for no traces); means and maxima in the SLO's unit and
+    rounding, as calls.csv's."""
+    with open("endpoints.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["result", "rank", "endpoint", "traces_abnormal", "traces_normal", "mean_abnormal", "mean_normal",
+                    "max_abnormal", "max_normal", "live"])
+        for rank, (label, key) in enumerate([("*", None)] + [(service, service) for service, _ in _ranked(top_list, score_list)]):
+            r = rows.get(key)
+            if r is None:
+                continue
+            for e in r["entries"]:
+                w.writerow([label, rank, "(none)" if e[0] is None else e[0], int(e[1]), int(e[2])] +
+                           _mean_max(e[1:3], e[3:5], e[5:7]) + [int(r["live"])])
+
+
 # ------------------------------------------------------------------------------------------- the table
 @dataclass(frozen=True)
 class Kind:
@@ -658,7 +758,9 @@ class Kind:
     slot of the batch answer (table, slot) to what ``window`` gives for an op, and ``write`` puts such rows
     into the kind's file.  ``head`` names a parameter that the sweep plan keeps ahead of its answers and that
     the writer takes after the rows (latency's q).  ``quantiles``: the (batch, window) forms that take the
-    parameters when an option of the keyword put a "q" among them (timeline_q), where the kind has such forms."""
+    parameters when an option of the keyword put a "q" among them (timeline_q), where the kind has such forms.
+    ``variants``: {by: (key, batch, window, row, write)}, the forms that take the parameters when an option of the
+    keyword put that "by" among them (kind_by); "by" chooses only, ``kwargs`` drops it from the call."""
     keyword: str
     key: str
     check: Callable
@@ -669,20 +771,44 @@ class Kind:
     write: Callable
     head: str | None = None
     quantiles: tuple | None = None
+    variants: dict | MappingProxyType | None = None
+
+    def _form(self, params):
+        """(key, batch, window, row, write) of the forms that take ``params``: the kind's own; its ``quantiles``
+        forms with a "q" among them; the ``variants`` record of their "by" (a second grouping of the kind, chosen
+        by an option of the keyword: {by: (key, batch, window, row, write)})."""
+        if self.variants is not None and params.get("by") in self.variants:
+            return self.variants[params["by"]]
+        if self.quantiles is not None and "q" in params:
+            return (self.key,) + tuple(self.quantiles) + (self.row, self.write)
+        return self.key, self.batch, self.window, self.row, self.write
+
+    @property
+    def keys(self):
+        """Every key the kind's forms leave an answer under."""
+        return (self.key,) + tuple(v[0] for v in (self.variants or {}).values())
+
+    def key_for(self, params):
+        """The key of the answer (and the stem of the file) of the form that takes ``params``."""
+        return self._form(params)[0]
 
     def batch_for(self, params):
         """The batch entry that takes ``params``."""
-        return self.quantiles[0] if self.quantiles is not None and "q" in params else self.batch
+        return self._form(params)[1]
 
     def window_for(self, params):
         """The one-window form that takes ``params``."""
-        return self.quantiles[1] if self.quantiles is not None and "q" in params else self.window
+        return self._form(params)[2]
 
-    def names(self, table, rows):
+    def kwargs(self, params):
+        """``params`` as the keywords of batch_for / window_for: without "by", which only chooses the form."""
+        return {k: v for k, v in params.items() if k != "by"}
+
+    def names(self, table, rows, params=MappingProxyType({})):
         """One window's batch answer {code: slot} as the writer's rows: by pod-op name where the table has names
-        (the lead ops None and -1 stay), each slot through ``row``."""
-        names = table.podop_names
-        return {(c if c is None or c < 0 or names is None else names[c]): self.row(table, r) for c, r in rows.items()}
+        (the lead ops None and -1 stay), each slot through the form's ``row``."""
+        names, row = table.podop_names, self._form(params)[3]
+        return {(c if c is None or c < 0 or names is None else names[c]): row(table, r) for c, r in rows.items()}
 
     def plan_value(self, params, by_m):
         """What sweep_rank leaves in the plan under ``key``: the answers {m: the batch's dict}."""
@@ -694,14 +820,16 @@ class Kind:
 
     def file(self, top_list, score_list, rows, params):
         """Rewrite the kind's file beside result.csv."""
-        self.write(top_list, score_list, rows, *(() if self.head is None else (params[self.head],)))
+        self._form(params)[4](top_list, score_list, rows, *(() if self.head is None else (params[self.head],)))
 
 
 KINDS = (
     Kind("latency", "latency", lambda v: {"q": _latency_args(*v)[0], "what": v[1]}, (), windows_latency, op_latency,
          _latency_row, _write_latency, head="q"),   # (its value: the pair (latency, latency_what))
-    Kind("kind_breakdown", "kinds", lambda m: {"m": _kind_m(m)}, (None,), windows_kind_breakdown, window_kinds,
-         _kind_row, _write_kinds),
+    Kind("kind_breakdown", "kinds", _kind_params, (None,), windows_kind_breakdown, window_kinds, _kind_row, _write_kinds,
+         variants=MappingProxyType({"endpoint": ("endpoints", windows_endpoints, window_endpoints, _endpoint_row,
+                                                 _write_endpoints)})),
+    # (its value: the keyword, or a _KindAsk with kind_by)
     Kind("call_edges", "calls", lambda m: {"m": _call_m(m)}, (), windows_call_edges, window_calls, _call_row,
          _write_calls),
     Kind("timeline", "timeline", _timeline_params, (-1,), windows_timeline, window_timeline, _timeline_row,
@@ -724,14 +852,23 @@ NOTHING = Evidence()
 
 
 def evidence_request(*, exemplars=None, exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                     call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
+                     call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self", kind_by="kind"):
     """The drivers' evidence keywords (online_anomaly_detect_RCA's docstring has each) checked into one
     Evidence; ValueError for a bad one, before any device work.  None means "not asked".  timeline_q and
-    timeline_what are options of the timeline kind: its parameters are {"buckets": B} without them."""
+    timeline_what are options of the timeline kind: its parameters are {"buckets": B} without them.  kind_by is an
+    option of the kind_breakdown kind: "kind" leaves its parameters {"m": m}, "endpoint" makes them {"m": m, "by":
+    "endpoint"} -- the window's traces grouped by entry operation (windows_endpoints, endpoints.csv) in place of
+    the trace kinds."""
     exemplar_kinds = check_exemplar_kinds(exemplar_kinds, exemplars)
     if exemplars is not None:
         exemplars = check_exemplar_m(exemplars)
     _what_code(timeline_what)
+    if not isinstance(kind_by, str) or kind_by not in ("kind", "endpoint"):
+        raise ValueError(f"kind_by must be 'kind' or 'endpoint', not {kind_by!r}")
+    if kind_by != "kind":
+        if kind_breakdown is None:
+            raise ValueError("kind_by needs kind_breakdown (the entries per op)")
+        kind_breakdown = _KindAsk(kind_breakdown, kind_by)
     if timeline_q is not None and timeline is None:
         raise ValueError("timeline_q needs timeline (the number of time buckets)")
     if timeline is not None and (timeline_q is not None or timeline_what != "self"):

@@ -26,10 +26,11 @@ from . import _lib
 from . import evidence as ev   # (the drivers read ev.KINDS when they are called)
 from ._lib import SPECTRUM_METHODS, ptr
 from .anormaly_detector import slo_arrays, system_anomaly_detect, trace_list_partition  # noqa: F401
-from .evidence import (NOTHING, _detect_state, _latency_ms, _ranked, _write_calls, _write_kinds,  # noqa: F401
-                       _write_latency, _write_replicas, _write_timeline, evidence_request, op_latency, window_calls,
-                       window_kinds, window_replicas, window_timeline, window_timeline_q, windows_call_edges,
-                       windows_kind_breakdown, windows_latency, windows_replicas, windows_timeline, windows_timeline_q)
+from .evidence import (NOTHING, _detect_state, _latency_ms, _ranked, _write_calls, _write_endpoints,  # noqa: F401
+                       _write_kinds, _write_latency, _write_replicas, _write_timeline, evidence_request, op_latency,
+                       window_calls, window_endpoints, window_kinds, window_replicas, window_timeline, window_timeline_q,
+                       windows_call_edges, windows_endpoints, windows_kind_breakdown, windows_latency, windows_replicas,
+                       windows_timeline, windows_timeline_q)
 from .graph import check_converge_args, check_exemplar_kinds, check_exemplar_m, check_exemplar_ops
 from .pagerank import ITERATIONS, trace_pagerank
 from .preprocess_data import (PagerankGraph, SpanStream, _quantile_args, get_operation_duration_data, get_operation_slo,  # noqa: F401
@@ -166,7 +167,7 @@ def sweep_chain(plan):
 
 def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None, exemplar_kinds=False, *, latency=None,
                latency_what="self", kind_breakdown=None, call_edges=None, timeline=None, replicas=None, timeline_q=None,
-               timeline_what="self"):
+               timeline_what="self", kind_by="kind"):
     """Every ranked window of the chain in ONE mr_windows_batch_ex call: {m: (codes, scores, ...)}.
     exemplars, exemplar_kinds: rank_windows' keywords (a 7th element per window).
     The evidence keywords are online_anomaly_detect_RCA's: each asked kind makes ONE batch call over the
@@ -176,18 +177,21 @@ def sweep_rank(plan, events, precision="fp64", iters=ITERATIONS, exemplars=None,
     call_edges: plan["calls"] = {m: windows_call_edges' dict};
     timeline: plan["timeline"] = {m: windows_timeline's dict}, the window's own traces (-1) first -- with
     timeline_q its slots carry "q" and "quantile" too, and timeline_what chooses their value;
+    kind_by="endpoint" (with kind_breakdown): plan["endpoints"] = {m: windows_endpoints' dict}, the whole window
+    (None) first, in place of plan["kinds"];
     replicas: plan["replicas"] = {m: windows_replicas' dict}."""
     return _sweep_rank(plan, events, precision, iters,
                        evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                         latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
                                         timeline=timeline, replicas=replicas, timeline_q=timeline_q,
-                                        timeline_what=timeline_what))
+                                        timeline_what=timeline_what, kind_by=kind_by))
 
 
 def _sweep_rank(plan, events, precision, iters, evidence):
     """sweep_rank for a checked request."""
     for kind in ev.KINDS:
-        plan.pop(kind.key, None)
+        for key in kind.keys:
+            plan.pop(key, None)
     todo = [e[1] for e in events if e[0] == "window" and e[4]]
     width = plan["step_n"] * plan["grain"]
     if not todo:
@@ -197,8 +201,9 @@ def _sweep_rank(plan, events, precision, iters, evidence):
     ranked = rank_windows(plan["ctx"], wins, precision=precision, iters=iters, exemplars=evidence.exemplars,
                           exemplar_kinds=evidence.exemplar_kinds)
     for kind, params in evidence.kinds:
-        answer = kind.batch_for(params)(plan["ctx"], wins, [list(kind.lead) + r[0].tolist() for r in ranked], **params)
-        plan[kind.key] = kind.plan_value(params, dict(zip(todo, answer)))
+        answer = kind.batch_for(params)(plan["ctx"], wins, [list(kind.lead) + r[0].tolist() for r in ranked],
+                                        **kind.kwargs(params))
+        plan[kind.key_for(params)] = kind.plan_value(params, dict(zip(todo, answer)))
     return dict(zip(todo, ranked))
 
 
@@ -266,12 +271,14 @@ def _sweep_emit(plan, events, results, evidence):
                     for c, lst in results[mm][6].items()}
             _write_exemplars(top_list, score_list, rows, evidence.exemplar_kinds)
         for kind, params in evidence.kinds:   # (the batch's answer, by name)
-            kind.file(top_list, score_list, kind.names(plan["table"], kind.answers(plan[kind.key])[mm]), params)
+            kind.file(top_list, score_list,
+                      kind.names(plan["table"], kind.answers(plan[kind.key_for(params)])[mm], params), params)
 
 
 def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITERATIONS, exemplars=None,
                               exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None,
-                              call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
+                              call_edges=None, timeline=None, replicas=None, timeline_q=None, timeline_what="self",
+                              kind_by="kind"):
     """online_rca.online_anomaly_detect_RCA (online_rca.py:155-216): 5-minute windows, a triggered
     window advances by 9 minutes; the detector's lists are unpacked swapped (T1), an empty
     window makes the unpacking raise TypeError (T2); result.csv is rewritten per trigger.
@@ -309,6 +316,16 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     distinct pod-ops.  From ONE windows_kind_breakdown call over the triggered windows on the sweep
     path, a call per window otherwise; tables whose window times vary within a trace are not covered
     (the call raises).  stdout and result.csv do not change; without it no file is written.
+
+    kind_by (with kind_breakdown): "kind" (the default: kinds.csv as above) or "endpoint": every trigger rewrites
+    ``endpoints.csv`` instead (columns result, rank, endpoint, traces_abnormal, traces_normal, mean_abnormal,
+    mean_normal, max_abnormal, max_normal, live; kinds.csv is not written): which user-facing endpoints are hit --
+    first the whole window's m endpoints with the most abnormal traces (``result`` = ``*``, rank 0), then for each
+    op of result.csv, in its order, the m such endpoints among the traces that hold a span of the op, each trace
+    once.  A trace's endpoint is the pod-op of its longest root span (``(none)`` without one); mean / max are of
+    endTime - startTime (the SLO's unit and rounding); ``live`` the slot's endpoints with a trace.  From ONE
+    windows_endpoints call over the triggered windows on the sweep path, a call per window otherwise.  Any other
+    value, or "endpoint" without kind_breakdown, is a ValueError.
 
     call_edges: an integer m (1..32): every trigger also rewrites ``calls.csv`` beside result.csv
     (columns result, rank, direction, peer, calls_abnormal, calls_normal, mean_abnormal, mean_normal,
@@ -350,7 +367,8 @@ def online_anomaly_detect_RCA(data, slo, operation_list, *, ctx=None, iters=ITER
     check_converge_args(0.0, iters, 1)
     evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                 latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
-                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what)
+                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what,
+                                kind_by=kind_by)
     window_normal = pd.Timedelta(minutes=5)
     window_abnormal = pd.Timedelta(minutes=4)
     start = data["startTime"].min()
@@ -395,8 +413,8 @@ def _window_loop(data, slo, operation_list, current_time, end, iters=ITERATIONS,
                                         distinct_kinds=evidence.exemplar_kinds) if top_list else {}
                 _write_exemplars(top_list, score_list, rows, evidence.exemplar_kinds)
             for kind, params in evidence.kinds:
-                kind.file(top_list, score_list, kind.window_for(params)(data, start_time, end_time, slo, top_list, **params),
-                          params)
+                kind.file(top_list, score_list,
+                          kind.window_for(params)(data, start_time, end_time, slo, top_list, **kind.kwargs(params)), params)
             current_time += window_abnormal
         current_time += window_normal
     return current_time
@@ -414,7 +432,7 @@ class RCAStream:
     (mr_spans_ingest) and runs the chain's new windows as one sweep + one batched ranking.
     iters: the PageRank iterations of every window, as online_anomaly_detect_RCA's.  The evidence keywords
     are its keywords too, each file rewritten at every trigger: exemplars, exemplar_kinds (exemplars.csv);
-    latency, latency_what (latency.csv); kind_breakdown (kinds.csv); call_edges (calls.csv); timeline
+    latency, latency_what (latency.csv); kind_breakdown (kinds.csv; with kind_by="endpoint" endpoints.csv); call_edges (calls.csv); timeline
     (timeline.csv), timeline_q (timeline_q.csv), timeline_what; replicas (replicas.csv).  They are kept
     checked, as one request, in ``evidence``."""
 
@@ -423,12 +441,12 @@ class RCAStream:
 
     def __init__(self, slo, operation_list, *, ctx=None, device_append=True, iters=ITERATIONS, exemplars=None,
                  exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-                 timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
+                 timeline=None, replicas=None, timeline_q=None, timeline_what="self", kind_by="kind"):
         check_converge_args(0.0, iters, 1)
         self.evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                          latency_what=latency_what, kind_breakdown=kind_breakdown,
                                          call_edges=call_edges, timeline=timeline, replicas=replicas,
-                                         timeline_q=timeline_q, timeline_what=timeline_what)
+                                         timeline_q=timeline_q, timeline_what=timeline_what, kind_by=kind_by)
         self.slo, self.operation_list, self.iters = slo, operation_list, iters
         self.ctx = ctx or _lib.default_context()
         self.data = None          # retained spans as a DataFrame (host mode only)
@@ -591,7 +609,7 @@ def window_exemplars(data, start_time, end_time, slo, ops, *, m=5, iters=ITERATI
 def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="dstar2", precision="fp64", ctx=None,
                table=None, dev=None, iters=ITERATIONS, tol=None, check_every=5, info=None, exemplars=None,
                exemplar_kinds=False, latency=None, latency_what="self", kind_breakdown=None, call_edges=None,
-               timeline=None, replicas=None, timeline_q=None, timeline_what="self"):
+               timeline=None, replicas=None, timeline_q=None, timeline_what="self", kind_by="kind"):
     """One RCA window entirely on the device (mr_rca_window_ex).  Returns a dict with the top list
     (pod-op names), scores, the detector counts and the edges traversed by the two PageRanks.
 
@@ -609,7 +627,8 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     The other evidence keywords are online_anomaly_detect_RCA's; each adds one key for the ops of the top list
     and leaves every other key what it is:
     latency (with latency_what): ``"latency"``, op_latency's dict;
-    kind_breakdown: ``"kinds"``, window_kinds' dict -- the whole window (key None), then the ops;
+    kind_breakdown: ``"kinds"``, window_kinds' dict -- the whole window (key None), then the ops; with
+    kind_by="endpoint" the key is ``"endpoints"`` instead, window_endpoints' dict in the same order;
     call_edges: ``"calls"``, window_calls' dict;
     timeline: ``"timeline"``, window_timeline's dict -- the window's own traces (key -1), then the ops; with
     timeline_q (a q as latency's) every slot carries ``"q"`` and ``"quantile"`` ([bucket][side][q], raw duration
@@ -618,7 +637,8 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
     tol = _iter_args(iters, tol, check_every, info, dict)
     evidence = evidence_request(exemplars=exemplars, exemplar_kinds=exemplar_kinds, latency=latency,
                                 latency_what=latency_what, kind_breakdown=kind_breakdown, call_edges=call_edges,
-                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what)
+                                timeline=timeline, replicas=replicas, timeline_q=timeline_q, timeline_what=timeline_what,
+                                kind_by=kind_by)
     exemplars = evidence.exemplars
     ctx = ctx or _lib.default_context()
     if table is None or dev is None:
@@ -650,8 +670,8 @@ def rca_window(data, start_time, end_time, slo, *, top_max=5, spectrum_method="d
                                             precision=precision, ctx=ctx, table=table, dev=dev,
                                             distinct_kinds=evidence.exemplar_kinds) if m else {}
     for kind, params in evidence.kinds:
-        res[kind.key] = kind.window_for(params)(data, start_time, end_time, slo, res["top"], ctx=ctx, table=table, dev=dev,
-                                                **params)
+        res[kind.key_for(params)] = kind.window_for(params)(data, start_time, end_time, slo, res["top"], ctx=ctx,
+                                                            table=table, dev=dev, **kind.kwargs(params))
     return res
 
 

@@ -106,6 +106,15 @@ class DeviceSpans:
         ctx.check(lib.mr_spans_upload(ctx.h, C.byref(cols), C.byref(h)), "mr_spans_upload")
         self.ctx, self.h, self.table = ctx, h, table
 
+    def entry_ops(self):
+        """The entry operation of every trace (mr_spans_entry_ops; csrc/mr_endpoints.hip): an int32 vector over
+        the trace codes, the pod-op code of the trace's longest root span (a row without a parent in the table;
+        ties to the first row), _lib.MR_EP_NONE for a trace without a root row.  Computed on the device at the
+        first call and kept with the table; a trace shard is not covered (RuntimeError from the library)."""
+        ep = np.zeros(max(self.table.n_traces, 1), np.int32)
+        self.ctx.check(_lib.load().mr_spans_entry_ops(self.ctx.h, self.h, ptr(ep, C.c_int32)), "mr_spans_entry_ops")
+        return ep[:self.table.n_traces]
+
     def close(self):
         # a destroyed context has freed its handles already (mr_ctx_destroy)
         if getattr(self, "h", None) and getattr(getattr(self, "ctx", None), "h", None):
