@@ -416,7 +416,7 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
     std::vector<IxBuild> bx(2 * (size_t)n);      //  kernels enqueued on them run first)
     // the detector inside the index pass's first launch for tables up to MR_DET_FUSE_MAX traces
     // (default 65536; measured: C3's 20k traces +2%, C2's 200k -3% -- the fused launch's tiles
-    // are the detector's 256 traces, 8x k_ix_sel_scan2's, and its look-back chains 8x longer).
+    // are the detector's 256 traces, 8x k_ix_sel_scan2_b's, and its look-back chains 8x longer).
     // MR_NO_DET_FUSE: never.  (Both read per call.)
     const char* fm = getenv("MR_DET_FUSE_MAX");
     const bool no_fuse = getenv("MR_NO_DET_FUSE") != nullptr;
@@ -436,93 +436,83 @@ static int win_chunk_build_async(mr_ctx* ctx, const WinIn* in, int n, int precis
         w.ga = new mr_graph();
         w.ga->ctx = ctx;
     }
-    // the whole chunk's index pass in one launch per stage when every window allows it (and the
-    // windows agree on the detector fusion), else window by window.  Tables with a layout order
-    // (mr_spans.lo_ok): the layout-order build (mr_lo_launch_batch), its kind histograms in one
-    // zeroed buffer
-    bool batched = false, lo = false;
+    // The chunk's builds, tier by tier (each falls to the next on MR_ERR_STATE, which every tier
+    // returns before it has launched anything):
+    //   1. tables with a layout order (mr_spans.lo_ok), unless MR_NO_LO_WIN: the layout-order batch
+    //      (mr_lo_launch_batch), its kind histograms in one zeroed buffer;
+    //   2. the two-graph index pass (mr_ix_launch2_batch): the whole chunk in one launch per stage
+    //      when its windows agree on the detector fusion, else window by window;
+    //   3. a window outside that pass's limits, or MR_NO_IX2: the detector, then a build per mask.
+    bool lo = false;
     DBuf<uint32_t> zw;
-    std::vector<const mr_spans*> sps((size_t)n);   // (the layout-order build's arguments: a window may be rebuilt)
+    std::vector<const mr_spans*> sps((size_t)n);   // (kept: a layout-order window may be rebuilt)
+    std::vector<uint8_t*> sts((size_t)n);
     std::vector<mr_graph*> g0((size_t)n), g1((size_t)n);
     std::vector<IxBuild*> b0((size_t)n), b1((size_t)n);
     std::vector<int64_t*> outs((size_t)n);
     std::vector<uint32_t*> zs((size_t)n);
-    {
-        bool ok = getenv("MR_NO_LO_WIN") == nullptr;   // (A/B and tests, read per call)
-        int64_t nzw = 0;
-        for (int k = 0; k < n && ok; ++k) {
-            ok = in[k].s->lo_ok && mr_lo_fits(in[k].s);
-            if (ok) nzw += mr_lo_zero_words(in[k].s);
-        }
-        if (ok) {
-            MR_TRY(zw.zero(ctx, (size_t)nzw));
-            int64_t zo = 0;
-            for (int k = 0; k < n; ++k) {
-                sps[(size_t)k] = in[k].s;
-                g0[(size_t)k] = in[k].w->gn;
-                g1[(size_t)k] = in[k].w->ga;
-                b0[(size_t)k] = &bx[2 * (size_t)k];
-                b1[(size_t)k] = &bx[2 * (size_t)k + 1];
-                outs[(size_t)k] = wb.p + (size_t)k * WW + CW;
-                zs[(size_t)k] = zw.p + zo;
-                zo += mr_lo_zero_words(in[k].s);
-            }
-            const int rcl = mr_lo_launch_batch(ctx, n, sps.data(), g0.data(), g1.data(), b0.data(), b1.data(), outs.data(),
-                                               dis.data(), zs.data());
-            if (rcl != MR_ERR_STATE) MR_TRY(rcl);
-            batched = lo = rcl == MR_OK;
-        }
+    bool lo_ok = getenv("MR_NO_LO_WIN") == nullptr, same = true;   // (A/B and tests, read per call)
+    int64_t nzw = 0;
+    for (int k = 0; k < n; ++k) {
+        sps[(size_t)k] = in[k].s;
+        sts[(size_t)k] = dst[(size_t)k].p;
+        g0[(size_t)k] = in[k].w->gn;   // "normal" graph = detector's abnormal traces
+        g1[(size_t)k] = in[k].w->ga;
+        b0[(size_t)k] = &bx[2 * (size_t)k];
+        b1[(size_t)k] = &bx[2 * (size_t)k + 1];
+        outs[(size_t)k] = wb.p + (size_t)k * WW + CW;
+        lo_ok = lo_ok && in[k].s->lo_ok && mr_lo_fits(in[k].s);
+        if (lo_ok) nzw += mr_lo_zero_words(in[k].s);
+        same = same && fz[(size_t)k] == fz[0];
     }
-    if (n >= 2 && !batched) {
-        bool same = true;
-        for (int k = 1; k < n; ++k) same = same && fz[(size_t)k] == fz[0];
-        if (same) {
-            std::vector<const mr_spans*> sps((size_t)n);
-            std::vector<uint8_t*> sts((size_t)n);
-            std::vector<mr_graph*> g0((size_t)n), g1((size_t)n);
-            std::vector<IxBuild*> b0((size_t)n), b1((size_t)n);
-            std::vector<int64_t*> outs((size_t)n);
-            for (int k = 0; k < n; ++k) {
-                sps[(size_t)k] = in[k].s;
-                sts[(size_t)k] = dst[(size_t)k].p;
-                g0[(size_t)k] = in[k].w->gn;
-                g1[(size_t)k] = in[k].w->ga;
-                b0[(size_t)k] = &bx[2 * (size_t)k];
-                b1[(size_t)k] = &bx[2 * (size_t)k + 1];
-                outs[(size_t)k] = wb.p + (size_t)k * WW + CW;
-            }
-            const int rcb = mr_ix_launch2_batch(ctx, n, sps.data(), sts.data(), g0.data(), g1.data(), b0.data(), b1.data(),
-                                                outs.data(), dis.data(), fz[0] != 0);
-            if (rcb != MR_ERR_STATE) MR_TRY(rcb);
-            batched = rcb == MR_OK;
+    if (lo_ok) {
+        MR_TRY(zw.zero(ctx, (size_t)nzw));
+        int64_t zo = 0;
+        for (int k = 0; k < n; ++k) {
+            zs[(size_t)k] = zw.p + zo;
+            zo += mr_lo_zero_words(in[k].s);
         }
+        const int rcl = mr_lo_launch_batch(ctx, n, sps.data(), g0.data(), g1.data(), b0.data(), b1.data(), outs.data(),
+                                           dis.data(), zs.data());
+        if (rcl != MR_ERR_STATE) MR_TRY(rcl);
+        lo = rcl == MR_OK;
     }
-    for (int k = 0; k < n && !batched; ++k) {
+    auto pass2 = [&](int k0, int m, bool fuse) {   // windows [k0, k0 + m) through the two-graph pass
+        return mr_ix_launch2_batch(ctx, m, &sps[(size_t)k0], &sts[(size_t)k0], &g0[(size_t)k0], &g1[(size_t)k0],
+                                   &b0[(size_t)k0], &b1[(size_t)k0], &outs[(size_t)k0], &dis[(size_t)k0], fuse);
+    };
+    // the whole chunk in one call; refused (or the windows disagree on the fusion): window by window
+    bool chunk_done = lo;
+    if (!chunk_done && same) {
+        const int rcb = pass2(0, n, fz[0] != 0);
+        if (rcb != MR_ERR_STATE) MR_TRY(rcb);
+        chunk_done = rcb == MR_OK;
+    }
+    // (a chunk of one window has had its call above.  Under MR_NO_IX2 every call below is refused
+    // again: each returns before it allocates anything.)
+    const bool retry = !(same && n == 1);
+    for (int k = 0; k < n && !chunk_done; ++k) {
+        if (retry) {
+            const int rc2 = pass2(k, 1, fz[(size_t)k] != 0);
+            if (rc2 != MR_ERR_STATE) {
+                MR_TRY(rc2);
+                continue;
+            }
+        }
+        // tier 3: this window mask by mask
+        // (the graphs take EVERY row of the selected traces: get_pagerank_graph(list, data),
+        // online_rca.py:180,185 / preprocess_data.py:148)
         const mr_spans* s = in[k].s;
-        WinRun& w = *in[k].w;
         const int32_t NT = s->n_traces;
         int64_t* wk = wb.p + (size_t)k * WW;
-        const DetIn& di = dis[(size_t)k];
-        IxBuild &bn = bx[2 * (size_t)k], &ba = bx[2 * (size_t)k + 1];
-        // (the graphs take EVERY row of the selected traces: get_pagerank_graph(list, data),
-        // online_rca.py:180,185 / preprocess_data.py:148).  Both from the states in one pass over
-        // the index when the table allows it, else one build per mask.
-        const bool fuse = fz[(size_t)k] != 0;
-        if (!fuse) MR_TRY(mr_detect_indexed_launch(ctx, s, in[k].t0, in[k].t1, in[k].a3, in[k].a3v, dst[(size_t)k].p,
-                                                   (unsigned long long*)wk));
-        const int rc2 = mr_ix_launch2(ctx, s, dst[(size_t)k].p, w.gn, w.ga, bn, ba, wk + CW, fuse ? &di : nullptr);
-        if (rc2 == MR_ERR_STATE) {
-            if (fuse) MR_TRY(mr_detect_indexed_launch(ctx, s, in[k].t0, in[k].t1, in[k].a3, in[k].a3v, dst[(size_t)k].p,
-                                                      (unsigned long long*)wk));
-            DBuf<uint8_t> m_abn, m_nor;
-            MR_TRY(m_abn.alloc(ctx, std::max(NT, 1)));
-            MR_TRY(m_nor.alloc(ctx, std::max(NT, 1)));
-            if (NT) hipLaunchKernelGGL(k_masks, dim3(cdiv(NT, 256)), dim3(256), 0, st, dst[(size_t)k].p, NT, m_abn.p, m_nor.p);
-            MR_TRY(mr_ix_launch(ctx, s, m_abn.p, w.gn, bn, wk + CW));   // "normal" graph = detector's abnormal traces
-            MR_TRY(mr_ix_launch(ctx, s, m_nor.p, w.ga, ba, wk + CW + 8));
-        } else {
-            MR_TRY(rc2);
-        }
+        MR_TRY(mr_detect_indexed_launch(ctx, s, in[k].t0, in[k].t1, in[k].a3, in[k].a3v, sts[(size_t)k],
+                                        (unsigned long long*)wk));
+        DBuf<uint8_t> m_abn, m_nor;
+        MR_TRY(m_abn.alloc(ctx, std::max(NT, 1)));
+        MR_TRY(m_nor.alloc(ctx, std::max(NT, 1)));
+        if (NT) hipLaunchKernelGGL(k_masks, dim3(cdiv(NT, 256)), dim3(256), 0, st, sts[(size_t)k], NT, m_abn.p, m_nor.p);
+        MR_TRY(mr_ix_launch(ctx, s, m_abn.p, g0[(size_t)k], *b0[(size_t)k], wk + CW));
+        MR_TRY(mr_ix_launch(ctx, s, m_nor.p, g1[(size_t)k], *b1[(size_t)k], wk + CW + 8));
     }
     ph0.reset();
     std::vector<int64_t> h((size_t)n * WW);

@@ -1,6 +1,6 @@
 // The window detector's per-block body (anormaly_detector.system_anomaly_detect on whole traces),
 // shared by k_ix_detect (mr_span_index.hip) and the fused detector + selection scan of a window's
-// two graph builds (k_ix_detect_scan2, mr_graph_build.hip).
+// two graph builds (k_ix_detect_b / k_ix_detect_scan2_b, mr_build_win.hip).
 //
 // A trace is in the window iff its trace-level [start, end] lies in [t0, t1] (T15); expect = sum
 // over the trace's service-ops in name order of count * (mean + 3 std) (sequential, no FMA: T14);

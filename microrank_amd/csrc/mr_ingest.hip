@@ -24,7 +24,7 @@
 #include "mr_prim.h"
 #include "mr_sort.h"
 
-int mr_spans_finish(mr_ctx* ctx, mr_spans* s);   // mr_graph_build.hip: spanID multimap + index
+int mr_spans_finish(mr_ctx* ctx, mr_spans* s);   // mr_spans.hip: spanID multimap + index
 
 namespace {
 constexpr int IB = 256;

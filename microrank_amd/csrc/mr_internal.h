@@ -557,7 +557,7 @@ int mr_graph_prepare(mr_ctx* ctx, mr_graph* g);   // derived arrays + segments a
 // several graphs' prepare in one launch per step when they allow it (keep: host descriptors)
 int mr_graph_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, int n, std::vector<unsigned char>& keep);
 int mr_graph_post_build(mr_ctx* ctx, mr_graph* g);   // trace-role fields + mr_graph_prepare after K1
-// An indexed K1 build between its launches and its size read-back (mr_graph_build.hip): several
+// An indexed K1 build between its launches and its size read-back (mr_build_ix.hip): several
 // builds (and the detector's counters) share one host round trip.  d_out receives 5 int64 words
 // (N, E, overflow, T, nnz); mr_ix_finish takes them (null when b.small is false) and prepares g.
 struct IxBuild {
@@ -574,10 +574,6 @@ struct IxBuild {
 };
 int mr_ix_launch(mr_ctx* ctx, const mr_spans* sp, const uint8_t* d_mask, mr_graph* g, IxBuild& b, int64_t* d_out);
 struct DetIn;   // (mr_detect_dev.h)
-int mr_ix_launch2(mr_ctx* ctx, const mr_spans* sp, const uint8_t* d_state, mr_graph* g0, mr_graph* g1, IxBuild& b0,
-                  IxBuild& b1, int64_t* d_out, const DetIn* det = nullptr);
-// the same for n <= 8 windows, one launch per stage (det: each window's detector inputs, fused
-// into the selection launch when fuse, else launched before it; null: states given)
 // A PageRank batch enqueued without its closing read-back (mr_windows_batch keeps one group of
 // windows in flight while it enqueues the next): its kernels' descriptors and error words stay
 // alive in the handle; finish waits for it and reports a kind-hash collision (rerun with the
@@ -603,6 +599,11 @@ void mr_pagerank_async_free(PrAsync* a);
 // *iters_done: the iterations every graph ran.
 int mr_pagerank_batch_report(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
                              int iters, int precision, double tol, int check_every, int32_t* iters_done, double* resid);
+// Both graphs of each of n <= 8 windows from the detector's states in one pass over the index, one
+// launch per stage (mr_build_win.hip; dets: each window's detector inputs, fused into the
+// selection launch when fuse, else launched before it; null: states given).  Sizes of graph j of
+// window k to d_outs[k] + 8 j.  MR_ERR_STATE, before anything is allocated or launched: MR_NO_IX2,
+// or a table past the one-pass limits -- the caller builds that window mask by mask (mr_ix_launch).
 int mr_ix_launch2_batch(mr_ctx* ctx, int n, const mr_spans* const* sps, uint8_t* const* d_states, mr_graph* const* g0s,
                         mr_graph* const* g1s, IxBuild* const* b0s, IxBuild* const* b1s, int64_t* const* d_outs,
                         const DetIn* dets, bool fuse);
@@ -637,7 +638,7 @@ struct MrWsWin {
 bool mr_win_spectrum_fits(int32_t Na, int32_t Nn, int32_t NP, int32_t k);
 int mr_win_spectrum_launch_n(mr_ctx* ctx, const MrWsWin* ws, int n, int method, int32_t k);
 int mr_ix_finish(mr_ctx* ctx, const mr_spans* sp, mr_graph* g, IxBuild& b, const int64_t* h);
-// Window graph pairs from the tables' layout order (sp->lo_ok; mr_graph_build.hip k_lo_build_b):
+// Window graph pairs from the tables' layout order (sp->lo_ok; mr_build_lo.hip k_lo_build_b):
 // detector, selection by layout position with the kind histograms, the graphs' per-op and per-edge
 // counts, the node pass; d_outs as mr_ix_launch2_batch's (N, E, overflow, T, nnz per graph; words 5
 // / 6 of each graph's 8 must be zero: the build's totals), dets[k] the window's detector inputs,
@@ -668,7 +669,7 @@ int mr_lo_prepare_batch(mr_ctx* ctx, mr_graph* const* gs, const mr_spans* const*
                         const int* anomaly, int n, double d, int precision, std::vector<unsigned char>& keep,
                         bool keep_tcode = false,    // keep_tcode: one more launch fills mr_graph.tcode
                         bool keep_tkid = false);    // ... and mr_graph.tkid (with keep_tcode only)
-// a graph of mr_ix_launch / mr_ix_launch2 finished WITHOUT its prepare: the caller prepares many
+// a graph of mr_ix_launch / mr_ix_launch2_batch finished WITHOUT its prepare: the caller prepares many
 // such graphs together (mr_graph_prepare_batch)
 int mr_ix_finish_unprepared(mr_ctx* ctx, const mr_spans* sp, mr_graph* g, IxBuild& b, const int64_t* h);
 int mr_pagerank_presetup(mr_ctx* ctx, mr_graph* g, int anomaly, double d, int precision, uint32_t flags);

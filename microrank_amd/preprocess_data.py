@@ -1,7 +1,7 @@
 """Drop-in for the reference module ``preprocess_data`` (preprocess_data.py).
 
 * ``get_pagerank_graph`` builds the op<->trace graph on the GPU (K1,
-  csrc/mr_graph_build.hip) from the int-coded span table and returns four lazy mappings
+  csrc/mr_graph_build.hip, mr_build_ix.hip) from the int-coded span table and returns four lazy mappings
   with the reference's key order and list contents.  Passing them straight to
   ``pagerank.trace_pagerank`` (what ``online_anomaly_detect_RCA`` does) keeps the graph in
   HBM: no dict is ever materialised.

@@ -588,7 +588,7 @@ def test_windows_batch_last_block_finish_bitwise(c3_window, monkeypatch):
 
 def test_windows_batch_fast_paths_equal_general_paths(c3_window, monkeypatch):
     """The window batch's fast paths -- the detector fused into the index pass's first launch
-    (k_ix_detect_scan2), both graphs built in one index pass (mr_ix_launch2) with dense edge ids,
+    (k_ix_detect_scan2_b), both graphs built in one index pass (mr_ix_launch2_batch) with dense edge ids,
     windows built in chunks and prepared together (mr_graph_prepare_batch), set up in batched
     launches over the group (pagerank_setup_batch) or over the chunk (mr_pagerank_presetup_n) --
     give the same rankings as the one-graph-at-a-time paths (MR_NO_IX2 / MR_EDGE_HASH /
@@ -919,7 +919,7 @@ def test_c2_windows_batch_groupings_agree(c2_batch, monkeypatch):
 
 def test_windows_batch_layout_order_equals_general_build(c3_window, monkeypatch):
     """The layout-order window build (tables indexed with their trace layout and exact kind
-    classes: k_lo_sel_b, k_lo_fill_b, ...) against the general per-window build (MR_NO_LO_WIN):
+    classes: k_lo_build_b, k_lo_pos_b, k_lo_reduce_b, ...) against the general two-graph build (MR_NO_LO_WIN):
     four C3-shaped windows of three tables and an empty window -- statuses, abnormal / normal
     counts and edges equal, top lists identical, DStar2 scores within 1e-12 (a tile's traces sum in
     another rotation); and one-window chunks (the layout-order launches with n = 1) bitwise equal
