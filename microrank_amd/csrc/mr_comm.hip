@@ -442,7 +442,7 @@ __global__ void k_peer_wait(unsigned long long* region, int nranks, unsigned lon
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
 }
 
-// ---- the exchange fused into k_fx_b (mr_pagerank.hip): mode 1 blocks push their ops' limbs into
+// ---- the exchange fused into k_fx_b (mr_pr_fxb_dev.h): mode 1 blocks push their ops' limbs into
 // every rank's slot for this rank and then store the round number (seq + 1) in a per-(source,
 // block) flag; mode 2 block b waits for flag (src, b) of every source -- only the words it sums --
 // and sums the R slots in rank order.  A flag holds the number of the last round its block pushed

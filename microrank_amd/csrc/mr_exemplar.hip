@@ -772,7 +772,7 @@ int mr_win_exemplars(mr_ctx* ctx, const MrWinEx* ws, int n, int32_t m, uint32_t 
             v.node_podop = g->node_podop.p;
             v.tkid = dk ? g->tkid.p : nullptr;
             v.kind = g->kind.p;
-            v.trun = g->lo_merged == 1 ? g->trun.p : nullptr;   // (as the iteration: mr_pagerank.hip describe step)
+            v.trun = g->lo_merged == 1 ? g->trun.p : nullptr;   // (as the iteration: gdev_pointers, mr_pr_launch.hip)
             v.v0 = 1.0 / (double)((int64_t)g->N + (int64_t)g->T);
             v.T = g->T;
             v.N = g->N;

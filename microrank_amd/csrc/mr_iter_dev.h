@@ -1,8 +1,10 @@
-// What the power iteration's kernels share across translation units (mr_pagerank.hip's iteration,
-// mr_pr_setup.hip's iteration state, mr_converge.hip's residual): the maxima ring and a graph's
-// device descriptor.
+// What the power iteration's kernels share across translation units (the iteration's kernels in
+// mr_pr_walk.hip, mr_pr_fxb.hip, mr_pr_tile_cold.hip and mr_pagerank.hip, mr_pr_setup.hip's iteration
+// state, mr_converge.hip's residual): the maxima ring, a graph's device descriptor, and the device
+// helpers that read the descriptor in more than one of those units.
 #pragma once
 #include "mr_internal.h"
+#include "mr_prim.h"
 
 // M_s / M_r per iteration live in MSH shards (an atomicMax per block or op on ONE word would
 // serialise ~2k same-address atomics per iteration); readers reduce the shards.
@@ -51,7 +53,7 @@ struct GDev {
     const int32_t* ss_par;
     void* q[2];
     double* sub[2];
-    float* suf[2];                 // su32 graphs: the same su as floats (k_tr_a EXT & 8 gathers these)
+    float* suf[2];                 // su32 graphs: the same su as floats (k_tr_a EXT & TR_X_W32 gathers these)
     double* spb[2];
     double* part;
     unsigned long long* mslot;
@@ -67,7 +69,7 @@ struct GDev {
     // wide fused graphs: k_tr_a's ops [0, NA) (NA = N otherwise); ops [NA, N) in ranges of
     // cold_rw ops whose rows (cold_part, blocks cold_rowbase[r] .. [r+1]) carry scale cx_scale
     int32_t NA, cold_rw;
-    int32_t ns_warm;               // k_tr_a EXT & 8: labels [NA, ns_warm) have their su in LDS (else NA)
+    int32_t ns_warm;               // k_tr_a EXT & TR_X_W32: labels [NA, ns_warm) have their su in LDS (else NA)
     int32_t su32;                  // fp32 wide graphs: su rounded to float where k_fx_b makes it
     const double* cold_acc;        // [T] per position: the cold half of the trace's su sum
     const unsigned long long* cold_part;
@@ -96,3 +98,56 @@ struct GDev {
 constexpr int32_t RESID_OPS = 4096;
 void mr_resid_launch(mr_ctx* ctx, const GDev* dv, int ng, int32_t blocks, int it, int stride, int slot, bool store,
                      unsigned long long* resid);
+
+// ---------------------------------------------------------------- device helpers of the iteration's kernels
+// (internal linkage: each unit that includes them inlines its own copy)
+namespace {
+
+// global-memory views of pointers read from GDev: loads through them compile to global_load
+// (vmcnt only) instead of flat_load, whose lgkmcnt share would make every LDS wait also wait
+// for outstanding HBM loads
+#define GLB __attribute__((address_space(1)))
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <class T>
+__device__ __forceinline__ const GLB T* gp(const T* p) { return (const GLB T*)p; }
+template <class T>
+__device__ __forceinline__ GLB T* gpw(T* p) { return (GLB T*)p; }
+
+// the graph owning a block of a launch: block_owner (mr_prim.h) over the launch's start offset --
+// blk0 k_iter_a, blk0b k_iter_b, blk0f k_tr_a, blk0fb k_fx_b -- non-decreasing over graphs (graphs
+// without blocks in a launch repeat it)
+// graph of a fused-launch block: ng <= 2 resolves from the scalar split (no memory hop)
+template <int32_t GDev::*FIRST>
+__device__ __forceinline__ int32_t fx_graph(const GDev* gs, int32_t ng, int32_t split) {
+    if (ng == 1) return 0;
+    if (ng == 2) return (int32_t)blockIdx.x >= split ? 1 : 0;
+    return block_owner<GDev, FIRST>(gs, ng, (int32_t)blockIdx.x);
+}
+
+// One collective per sharded iteration: the r' maximum of this rank travels with the per-op sums
+// in a one-hot slot per rank (its bit pattern, or the double itself in an fp64 sum: x + 0 = x),
+// so the SUM all-reduce also delivers every rank's maximum.  put: a wave reduces this rank's MSH
+// shards into slot[rank] and zeroes the other slots; take: the max over the slots joins the shards.
+template <class W>
+__device__ __forceinline__ void rmax_put(const GDev& G, const unsigned long long* Mnext, W* slots, int lane) {
+    const double m = wave_max(bits2d(Mnext[MSH + lane]));
+    for (int j = lane; j < G.nranks; j += WAVE) {
+        if constexpr (sizeof(W) == 8 && (W)0.5 == (W)0) slots[j] = j == G.rank ? (W)d2bits(m) : (W)0;
+        else slots[j] = j == G.rank ? (W)m : (W)0;
+    }
+}
+__device__ __forceinline__ void rmax_take_bits(const unsigned long long* slots, int n, unsigned long long* Mnext, int lane) {
+    unsigned long long b = 0ull;
+    for (int j = lane; j < n; j += WAVE) b = max(b, slots[j]);
+    const double m = wave_max(bits2d(b));
+    if (lane == 0) atomicMax(&Mnext[MSH], d2bits(m));
+}
+__device__ __forceinline__ void rmax_take_f64(const double* slots, int n, unsigned long long* Mnext, int lane) {
+    double b = 0.0;
+    for (int j = lane; j < n; j += WAVE) b = nmax(b, slots[j]);
+    const double m = wave_max(b);
+    if (lane == 0) atomicMax(&Mnext[MSH], d2bits(m));
+}
+
+}  // namespace

@@ -1,6 +1,8 @@
 // What the PageRank units share on the host side -- mr_pagerank.hip (the iteration and the public
-// entries), mr_pr_prepare.hip, mr_pr_kinds.hip, mr_pr_setup.hip, mr_pr_shard.hip, and nobody else:
-// the constants two of them need, the small helpers, and the functions one unit calls in another.
+// entries) and the units of its attempt (mr_pr_plan.hip, mr_pr_launch.hip, mr_pr_walk.hip,
+// mr_pr_fxb.hip, mr_pr_tile_cold.hip: what only those share is in mr_pr_iter.h), mr_pr_prepare.hip,
+// mr_pr_kinds.hip, mr_pr_setup.hip, mr_pr_shard.hip, and nobody else: the constants two of them
+// need, the small helpers, and the functions one unit calls in another.
 // Descriptor structs (PDev, SDev, LDev, ...) stay private to their unit.
 #pragma once
 #include <algorithm>
@@ -12,8 +14,11 @@
 // ---------------------------------------------------------------- constants of more than one unit
 constexpr int TB = 256;             // trace-role block size (one trace per thread)
 constexpr int LONG_PAIR = 32;       // tile pairs longer than this are summed by a whole wave
+constexpr int LDS_NODES = 8192;     // k_iter_a: su staged in LDS up to this many nodes (64 KiB)
+constexpr int VCAP = 2048;          // k_iter_a: trace-role ids staged per round in LDS (16 KiB of values)
+constexpr int WIDE_CT = 1024;       // k_cold_ops block size
 constexpr int TR_PAD = WAVE;   // k_tr_a's pad ids N .. N + 63 (su = 0)
-constexpr int FX_NMAX = 16384;      // the fused iteration's N (mr_pagerank.hip); wide graphs above
+constexpr int FX_NMAX = 16384;      // the fused iteration's N (k_tr_a / k_fx_b); wide graphs above
 #ifndef MR_WIDE_NA
 #define MR_WIDE_NA 10000
 #endif
@@ -23,7 +28,7 @@ constexpr int32_t WIDE_NA = MR_WIDE_NA;   // (WIDE_NA + TR_PAD) * 16 B + the hot
 #endif
 constexpr int TR_TIERS_EXT = 8;   // short-tile tiers of the EXT (kind-compressed / wide) variants
 #ifndef MR_TR_TIERS_W32
-#define MR_TR_TIERS_W32 5   // ... of the fp32 wide variant (EXT & 8: its pipelined cold registers; 6 spilled)
+#define MR_TR_TIERS_W32 5   // ... of the fp32 wide variant (EXT & TR_X_W32: its pipelined cold registers; 6 spilled)
 #endif
 constexpr int TR_TIERS_W32 = MR_TR_TIERS_W32;
 #ifndef MR_HOT_MAX
@@ -56,7 +61,9 @@ inline int32_t kern_n(const mr_graph* g) { return g->wide ? g->NA : g->N; }
 // ---------------------------------------------------------------- mr_pagerank.hip
 int mr_pagerank_batch_impl(mr_ctx* ctx, mr_graph* const* gs, const int* anomaly, int ng, double d, double alpha,
                            int iters, int precision, uint32_t flags, bool sharded = false, double* last_resid = nullptr);
-// k_tr_a's LDS image (TrLds) of a graph of N ops: every op's su fits beside the accumulator; the
+
+// ---------------------------------------------------------------- mr_pr_plan.hip
+// k_tr_a's LDS image (TrLds, mr_pr_walk.h) of a graph of N ops: every op's su fits beside the accumulator; the
 // hot-op mask sums fit too
 bool tr_su_fits(int32_t N);
 bool tr_hot_fits(int32_t N);

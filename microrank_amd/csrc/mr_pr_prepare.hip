@@ -1,7 +1,8 @@
 // Graph prepare for K2 (mr_graph_prepare, mr_graph_prepare_batch): derived arrays + segments after
 // structure upload -- the per-graph constants, the P_sr tiles (compressed sparse blocks) of
 // k_iter_a, the op relabelling by coverage (trace_num_list, pagerank.py:98-104), the wide split
-// (N > FX_NMAX) and the trace-parallel layout k_tr_a walks.  The iteration itself: mr_pagerank.hip.
+// (N > FX_NMAX) and the trace-parallel layout k_tr_a walks.  The iteration itself: mr_pagerank.hip
+// (its kernels: mr_pr_walk.hip, mr_pr_fxb.hip, mr_pr_tile_cold.hip; its plan: mr_pr_plan.hip).
 #include <algorithm>
 #include <cstdlib>
 

@@ -1,7 +1,8 @@
 // Trace-sharded graphs for K2 (mr_pagerank_sharded): the exchange that makes a rank's shard rank as
 // the whole graph does -- the op constants and call edges over the ranks (shard_exchange) and the
 // kind classes (pagerank.py:54-66) merged across ranks (shard_kinds).  The sharded iteration itself:
-// mr_pagerank.hip; the collectives: mr_comm.hip.
+// iterate (mr_pagerank.hip) around k_fx_b's / k_iter_b's modes 1 and 2 (mr_pr_fxb_dev.h,
+// mr_pr_tile_dev.h); the collectives: mr_comm.hip.
 #include <algorithm>
 
 #include "mr_pr_dev.h"

@@ -3,7 +3,7 @@
 ``trace_pagerank(operation_operation, operation_trace, trace_operation, pr_trace, anomaly)``
 returns ``(weight, trace_num_list)`` exactly like pagerank.py:15-112: two dicts in node
 order, weights as ``np.float64``, coverage counts as ``int``.  The work runs on the GPU
-(K2 in microrank_amd/csrc/mr_pagerank.hip and mr_pr_*.hip); nothing is computed on the host
+(K2 in microrank_amd/csrc/mr_pagerank.hip and mr_pr_*.hip: a file map is in DESIGN.md §3); nothing is computed on the host
 except the dict <-> index conversion for mappings that did not come from this package's
 ``get_pagerank_graph``.
 """

@@ -1,7 +1,7 @@
 """Trace-sharded PageRank over several processes.
 
 One process per GPU holds a shard of the traces (every span of a trace on one rank) over the
-global node index space.  ``mr_pagerank_sharded`` (csrc/mr_pagerank.hip, csrc/mr_pr_shard.hip)
+global node index space.  ``mr_pagerank_sharded`` (csrc/mr_pagerank.hip, csrc/mr_pr_shard.hip; the kernels' exchange modes: csrc/mr_pr_fxb_dev.h)
 exchanges, once per graph, the per-op span counts / children counts / coverage, the call edges and the trace-kind
 classes, and per iteration ONE all-reduce: the exact fixed-point P_sr r limbs (uint64 SUM) with
 every rank's max r' in a one-hot slot, so every rank ends with the weights the whole graph would

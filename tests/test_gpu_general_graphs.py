@@ -7,8 +7,8 @@ A graph uploaded with explicit rs arrays never takes the fused iteration: it run
 role over P_rs, tile role over the P_sr tiles) and k_iter_b, the tile build of mr_graph_prepare,
 the int32 kind kernels and the preference kernels with pr_trace / pr_len pointers.  The shapes are
 the smallest that reach each regime of those kernels; every case asserts on the host, from the
-arrays it uploads, that it does reach it (_regime mirrors the constants of mr_pagerank.hip
-and mr_pr_internal.h).
+arrays it uploads, that it does reach it (_regime mirrors the constants of mr_pr_internal.h,
+which the tile path's kernels in mr_pr_tile_dev.h read).
 
 Reference: the oracle (fp64 weights 1e-10 on every entry, an exact 0 stays an exact 0; fp32 1e-4;
 kinds and coverage exact; the preference bit for bit with exact_sums, within one fp32 ulp with
@@ -34,7 +34,7 @@ RTOL32 = 1e-4
 PREF_ULP = 1.2e-7  # tree vs sequential preference sums: <= 1 fp32 ulp (test_c2_scale_against_oracle)
 SEED = 3
 
-# mr_pagerank.hip / mr_pr_internal.h: trace-role block, ids staged per round, su in LDS up to,
+# mr_pr_internal.h (k_iter_a / k_iter_b: mr_pr_tile_dev.h): trace-role block, ids staged per round, su in LDS up to,
 # wave-per-pair above, u16 ids up to, fused iteration up to
 TB, VCAP, LDS_NODES, LONG_PAIR, U16_NODES, FX_NMAX = 256, 2048, 8192, 32, 65536, 16384
 

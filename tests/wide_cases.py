@@ -5,7 +5,7 @@ A graph with N > FX_NMAX ops ranks on the wide fused path: its WIDE_NA most cove
 k_tr_a's LDS walk, the other ("cold") entries run through k_cold_trace / k_cold_ops, one cold range
 per WIDE_RW_MAX cold ops.  A narrow fused graph keeps every op's su in LDS up to SU_LDS_NMAX ops
 ((N + 64) * 16 B <= 160 KB - 512 B); above it the launch leaves the su-in-LDS mode.  These constants
-mirror microrank_amd/csrc/mr_pr_internal.h, mr_pr_prepare.hip and mr_pagerank.hip; ``shape`` computes
+mirror microrank_amd/csrc/mr_pr_internal.h, mr_pr_prepare.hip and mr_pr_walk.h (WV_LDS_MAX); ``shape`` computes
 from the host arrays what the wide set-up makes of a graph, and tests/test_wide_cases.py asserts
 the facts each case stands for, so a generator change cannot quietly turn a case narrow.
 
